@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """bench.py -- training samples/sec of the MLP mini-batch SGD path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`); `--full` adds everything else
+it can measure: the per-kernel `roofline` pass, the host-batch rate, the CPU baseline, the other BASELINE configs (N = 1) and
+the dp variants (N > 1).  `--dump-outputs DIR` writes the weights and momentum the timed steps left as DIR/*.npy.
 
 A "step" is one gradientStep (SCE:297-346: forward + backward + [all-reduce] + momentum update)
 on one batch of synthetic 784-dim inputs already resident in HBM.  The workload at every N is
@@ -70,7 +74,7 @@ def parse_args(argv=None):
                     help="GEMM operand type (f32 = BASELINE configs[1], the headline; bf16 = configs[2]'s arithmetic)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the short same-run timings of BASELINE configs[0], [3], [4] (N=1 only; a few seconds)")
+                    help="--full: skip the short same-run timings of BASELINE configs[0], [3], [4] (N=1 only; a few seconds)")
     ap.add_argument("--dp-mode", choices=["auto", "graph", "eager"], default="auto",
                     help="data-parallel path: hipGraph replay of the resident batches, or eager steps; "
                          "auto = eager on more than one rank, graph for the one-rank --dp-path with RCCL")
@@ -103,10 +107,38 @@ def parse_args(argv=None):
     ap.add_argument("--variants-budget", type=float, default=600.0,
                     help="seconds all dp variants together may take: once spent, the remaining ones are skipped (reported as such)")
     ap.add_argument("--variant-child", action="store_true", help="(internal) this process measures ONE variant: no further children")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the per-kernel roofline pass, the host-batch rate, the CPU "
+                         "baseline, the other BASELINE configs (N = 1) and the dp variants (N > 1); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed (the flat weights and momentum a caller of the path "
+                         "reads back, float64) as DIR/<name>.npy")
     args = ap.parse_args(argv)
     if args.no_graph:
         args.dp_mode = "eager"
+    if args.dump_outputs is not None:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
     return args
+
+
+def absolute_dump_dir(argv):
+    """argv with the --dump-outputs directory made absolute: the children of this script run from the repository root."""
+    out = list(argv)
+    for i, a in enumerate(out):
+        if a == "--dump-outputs" and i + 1 < len(out):
+            out[i + 1] = os.path.abspath(out[i + 1])
+        elif a.startswith("--dump-outputs="):
+            out[i] = "--dump-outputs=" + os.path.abspath(a.split("=", 1)[1])
+    return out
+
+
+def dump_outputs(directory, net):
+    """What the timed steps computed, as a caller of the path receives it: the flat weights and momentum (get_weights /
+    get_momentum, float64; 4.3 MB together for the headline net)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "weights.npy"), np.asarray(net.get_weights(), dtype=np.float64))
+    np.save(os.path.join(directory, "momentum.npy"), np.asarray(net.get_momentum(), dtype=np.float64))
 
 
 # ---------------------------------------------------------------------------------------------
@@ -278,7 +310,7 @@ def dp_variant_specs(args):
     """(name, "single" | "group", argv) of every variant measured beside the headline at N > 1.  `single` = one process (the
     in-library forms own all N devices; `one GPU alone` is the same workload at N = 1); `group` = N ranks, one per GPU."""
     n, K, W = args.gpus, args.steps, args.warmup
-    tail = ["--no-cpu-baseline", "--no-other-configs", "--no-dp-variants", "--variant-child"]
+    tail = ["--no-cpu-baseline", "--no-other-configs", "--no-dp-variants", "--variant-child", "--full"]   # (--full: the roofline)
     if args.share_gpu:
         tail.append("--share-gpu")
     ranks = ["--gpus", str(n), "--steps", str(K), "--warmup", str(W), "--backend", args.backend] + tail
@@ -369,7 +401,7 @@ def launch(args, argv):
                 print("bench.py launcher: rank 0 printed %d lines instead of one" % len(lines), file=sys.stderr)
                 return 1
             text = lines[0]
-            if args.gpus > 1 and not args.no_dp_variants and not args.variant_child:
+            if args.gpus > 1 and args.full and not args.no_dp_variants and not args.variant_child:
                 text = merge_variants(text, args)
             print(text, flush=True)
             return 0
@@ -643,17 +675,21 @@ def library_worker(args):
     net.synchronize()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    # per-kernel roofline as on the rank path: the dispatches' own timestamps on replica 0 (every replica runs the same launches
-    # on its 128 rows), over a further pass of the same loop
-    nt = min(K, 256)
-    r0 = net.replicas[0]
-    r0.timing_enable(True)
-    net.train_range(((W + K) % N_BATCHES) * Bg, Bg, nt, STEP, MOMENTUM)
-    net.synchronize()
-    roofline = kernel_roofline(r0.timing_read, DIMS, BATCH, bf16, True, r0.step_launches == 2, dt / K * 1e6, nt)
-    r0.timing_enable(False)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, net)
+    roofline = None
+    if args.full:
+        # per-kernel roofline as on the rank path: the dispatches' own timestamps on replica 0 (every replica runs the same
+        # launches on its 128 rows), over a further pass of the same loop
+        nt = min(K, 256)
+        r0 = net.replicas[0]
+        r0.timing_enable(True)
+        net.train_range(((W + K) % N_BATCHES) * Bg, Bg, nt, STEP, MOMENTUM)
+        net.synchronize()
+        roofline = kernel_roofline(r0.timing_read, DIMS, BATCH, bf16, True, r0.step_launches == 2, dt / K * 1e6, nt)
+        r0.timing_enable(False)
     identical = net.replicas_identical()
-    cpu = None if args.no_cpu_baseline else cpu_baseline()
+    cpu = None if args.no_cpu_baseline or not args.full else cpu_baseline()
     line = {
         "metric": "training samples/sec, 784-300-100-10 MLP batch 128",
         "value": round(K * Bg / dt, 1), "unit": "samples/s", "n_gpus": n, "steps": K, "warmup": W,
@@ -701,7 +737,7 @@ def supervise_own_rank(args, argv):
             rc = 124
         if rc == 0:
             text = (out_text or "").strip()
-            if text and world > 1 and os.environ.get("RANK", "0") == "0" and not args.no_dp_variants and not args.variant_child:
+            if text and world > 1 and os.environ.get("RANK", "0") == "0" and args.full and not args.no_dp_variants and not args.variant_child:
                 time.sleep(2.0)   # (the other ranks' children left the barrier with this one's: let them release their devices)
                 try:
                     text = merge_variants(text.splitlines()[-1], args)
@@ -888,8 +924,10 @@ def worker(args, argv):
         t = torch.tensor([dt], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, net)   # (the replicas are identical: rank 0's state is every rank's)
 
-    # ---- per-kernel roofline: the dispatches' own begin/end timestamps, over the same step loop
+    # ---- --full: per-kernel roofline: the dispatches' own begin/end timestamps, over the same step loop
     roofline = None
     cpu = None
     host_rate = None
@@ -897,11 +935,12 @@ def worker(args, argv):
     # collective, so EVERY rank takes part (eagerly: kernels inside a replayed graph are not
     # timed); only rank 0 records and reports.
     nt = min(K, 1000) if dist is None else min(K, 256)
-    if rank == 0:
-        net.timing_enable(True)
-    run(W + K if dist is None else K, nt, eager=True)
-    barrier()
-    if rank == 0:
+    if args.full:
+        if rank == 0:
+            net.timing_enable(True)
+        run(W + K if dist is None else K, nt, eager=True)
+        barrier()
+    if rank == 0 and args.full:
         if headline_shape:
             roofline = kernel_roofline(net.timing_read, DIMS, BATCH, bf16, dist is not None, net.step_launches == 2, dt / K * 1e6, nt)
         else:
@@ -924,7 +963,7 @@ def worker(args, argv):
                 cpu = cpu_baseline()
 
     others = None
-    if rank == 0 and dist is None and not args.no_other_configs and not args.variant_child:
+    if rank == 0 and dist is None and args.full and not args.no_other_configs and not args.variant_child:
         net.close()
         others = other_configs()
 
@@ -966,7 +1005,7 @@ def worker(args, argv):
 
 
 def main():
-    argv = sys.argv[1:]
+    argv = absolute_dump_dir(sys.argv[1:])
     args = parse_args(argv)
     world_env = os.environ.get("WORLD_SIZE")
     if args.dp_impl == "library" and world_env is None:
@@ -983,7 +1022,7 @@ def main():
     # dp variants afterwards
     if is_dp and not supervised:
         plan = attempt_plan(args, args.gpus)
-        if plan[0][0] == "graph" or len(plan) > 1 or (world_env is not None and args.gpus > 1 and not args.no_dp_variants):
+        if plan[0][0] == "graph" or len(plan) > 1 or (world_env is not None and args.gpus > 1 and args.full and not args.no_dp_variants):
             sys.exit(supervise_own_rank(args, argv))
         args.dp_mode, args.dp_exchange = plan[0]
     if args.dp_exchange == "auto":

@@ -1,11 +1,10 @@
 """Writes tests/golden/reference_labels.json from the two label files the reference HOLDS
-(/root/reference/data/train-labels-idx1-ubyte, t10k-labels-idx1-ubyte) -- with logs/trainLog.csv the only
-reference-held data on this path (the image files are absent from the reference).  MNISTTrainer reads them at
+(data/train-labels-idx1-ubyte, data/t10k-labels-idx1-ubyte; committed beside this script, gzipped) -- with logs/trainLog.csv
+the only reference-held data on this path (the image files are absent from the reference).  MNISTTrainer reads them at
 MT:28-31 (open), MT:38-40 / MT:49-52 (magic 2049, count), MT:112-118 (one byte per label -> one-hot row).
 
-Run in the BUILD CONTAINER only (the reference does not travel to the GPU box); the JSON is data -- header
-integers, counts, a class histogram, the first 2 048 labels of each file, a checksum of the whole payload, and the
-labels at the rows the trainer's sampler draws first (NNT:143-168 with Random(1), NNT:42) -- not source text.
+The JSON is data -- header integers, counts, a class histogram, the first 2 048 labels of each file, a checksum of the
+whole payload, and the labels at the rows the trainer's sampler draws first (NNT:143-168 with Random(1), NNT:42) -- not source text.
 
     python -m tests.golden.make_label_fixture        # rewrites reference_labels.json
 
@@ -13,6 +12,7 @@ The parsing below is this script's own (struct + numpy): it must not depend on t
 draws come from the ORACLE's restatement (oracle/mlp_oracle.c), which tests/test_oracle.py pins to java.util.Random's
 documented LCG.
 """
+import gzip
 import json
 import os
 import struct
@@ -24,7 +24,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-REF_DATA = "/root/reference/data"
+REF_DATA = os.path.dirname(os.path.abspath(__file__))   # <name>.gz: the reference's data/<name>, gzipped
 FILES = {"train": "train-labels-idx1-ubyte", "t10k": "t10k-labels-idx1-ubyte"}
 OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "reference_labels.json")
 N_FIRST = 2048
@@ -40,7 +40,8 @@ def fnv1a64(data):
 
 
 def describe(path):
-    raw = open(path, "rb").read()
+    with gzip.open(path + ".gz") as f:
+        raw = f.read()
     magic, n = struct.unpack(">ii", raw[:8])          # MT:76-80: four bytes, big endian
     payload = raw[8:]
     lab = np.frombuffer(payload, dtype=np.uint8)

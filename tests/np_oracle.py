@@ -2,7 +2,7 @@
 reference's math.  It shares no code with oracle/mlp_oracle.c (which follows the Java loop
 nests sample by sample); the two must agree to ~1e-12 relative (tests/test_oracle.py).
 
-Citations: SCE = /root/reference/src/SoftmaxCrossEntropyNeuralNet.java, GNN = GeneralNeuralNet.java.
+Citations: SCE = the reference's src/SoftmaxCrossEntropyNeuralNet.java, GNN = GeneralNeuralNet.java.
 """
 import numpy as np
 

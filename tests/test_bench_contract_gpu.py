@@ -1,11 +1,13 @@
 """bench.py's output contract: exactly ONE line on stdout, a JSON object with the driver's keys
-plus the `roofline` and `cpu_baseline` objects (the latter null when skipped), on the plain
-single-process path and on the data-parallel path (RCCL, one rank)."""
+plus (`--full`) the `roofline` and `cpu_baseline` objects (the latter null when skipped), on the
+single-process path and on the data-parallel path (RCCL, one rank); a plain run (no `--full`)
+carries the headline only, and `--dump-outputs` writes what its timed steps computed."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -19,7 +21,7 @@ def run_bench(*flags, want_stderr=False):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(MASTER_ADDR="127.0.0.1", MASTER_PORT="29577")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "128", "--warmup", "64",
-                          "--no-cpu-baseline", *flags], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+                          "--no-cpu-baseline", "--full", *flags], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, out.stdout[:2000]
@@ -114,7 +116,7 @@ def test_bench_two_ranks_started_by_torch_distributed_run():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "GNN_BENCH_LAUNCHER")}
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                           "--master-port", "29533", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "128", "--warmup", "64",
-                          "--no-cpu-baseline", "--backend", "gloo", "--share-gpu"], capture_output=True, text=True, timeout=1200, env=env, cwd=ROOT)
+                          "--no-cpu-baseline", "--full", "--backend", "gloo", "--share-gpu"], capture_output=True, text=True, timeout=1200, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip().startswith("{")]
     assert len(lines) == 1, out.stdout[:2000]
@@ -164,7 +166,7 @@ def test_bench_capture_failure_under_external_launcher():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29591", RANK="0", LOCAL_RANK="0", WORLD_SIZE="1")
     env.pop("GNN_BENCH_LAUNCHER", None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "128", "--warmup", "64",
-                          "--no-cpu-baseline", "--dp-path", "--inject-capture-failure"],
+                          "--no-cpu-baseline", "--full", "--dp-path", "--inject-capture-failure"],
                          capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -189,3 +191,32 @@ def test_bench_library_data_parallel_rehearsal(reducer):
     r = line["roofline"]                      # as on the rank path: the kernel with the largest share of replica 0's step
     assert r is not None and r["bound"] in ("hbm", "mfma") and r["peak"] > 0 and "kernel" in r and "other" in r
     assert line["cpu_baseline"] is None      # --no-cpu-baseline; without the flag the library form reports it like the rank form
+
+
+def test_bench_plain_run_is_the_headline_and_dumps_its_outputs(tmp_path):
+    """The plain call shape (no --full): the same headline keys, nothing measured beside them, and --dump-outputs writes what the
+    timed steps left -- the flat weights and momentum -- identically from run to run (same arguments, same inputs)."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    dumps = []
+    for i in range(2):
+        d = tmp_path / ("run%d" % i)
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "96", "--warmup", "32",
+                              "--dump-outputs", str(d)], capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [l for l in out.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, out.stdout[:2000]
+        line = json.loads(lines[0])
+        assert line["metric"] == "training samples/sec, 784-300-100-10 MLP batch 128" and line["unit"] == "samples/s"
+        assert line["higher_is_better"] is True and line["dtype"] == "f32" and line["steps"] == 96 and line["warmup"] == 32
+        assert abs(line["value"] - 128 * 96 / (line["ms_per_step"] * 1e-3 * 96)) <= 0.01 * line["value"]
+        assert 0.5 * line["ms_per_step"] <= line["ms_per_step_events"] <= 1.05 * line["ms_per_step"]
+        assert line["roofline"] is None and line["cpu_baseline"] is None and line["other_configs"] is None
+        assert line["host_batch_samples_per_s"] is None
+        dumps.append({n: np.load(d / (n + ".npy")) for n in ("weights", "momentum")})
+        assert sorted(os.listdir(d)) == ["momentum.npy", "weights.npy"]
+        assert sum(os.path.getsize(d / f) for f in os.listdir(d)) <= 64 << 20
+    n_params = 784 * 300 + 300 * 100 + 100 * 10
+    for name in ("weights", "momentum"):
+        a, b = dumps[0][name], dumps[1][name]
+        assert a.dtype == np.float64 and a.shape == (n_params,) and np.isfinite(a).all() and np.abs(a).max() > 0
+        assert np.array_equal(a, b), name

@@ -114,8 +114,8 @@ def test_dp_variants_are_merged_and_a_failing_one_does_not_take_the_headline_dow
                                                             "roofline": {"bound": "hbm", "frac": 0.02, "kernel": "k"}}) + "\n"
     monkeypatch.setattr(b, "run_group", fake_group)
     monkeypatch.setattr(b, "run_single", fake_single)
-    args = b.parse_args(["--gpus", "8", "--steps", "50", "--warmup", "10"])
-    assert b.launch(args, ["--gpus", "8", "--steps", "50", "--warmup", "10"]) == 0
+    args = b.parse_args(["--gpus", "8", "--steps", "50", "--warmup", "10", "--full"])
+    assert b.launch(args, ["--gpus", "8", "--steps", "50", "--warmup", "10", "--full"]) == 0
     line = json.loads(capsys.readouterr().out.strip())
     assert line["value"] == 800.0 and line["n_gpus"] == 8           # the headline is the one-process-per-GPU RCCL form
     v = line["dp_variants"]
@@ -129,8 +129,8 @@ def test_dp_variants_are_merged_and_a_failing_one_does_not_take_the_headline_dow
     direct = next(v[n] for n in names if "library direct f32" in n)
     assert direct["value"] == 650.0 and direct["roofline"]["frac"] == 0.02 and direct["config"]["backend"] == "direct"
     # once the variants' time budget is spent the rest is skipped, and says so
-    args = b.parse_args(["--gpus", "8", "--steps", "50", "--warmup", "10", "--variants-budget", "0"])
-    assert b.launch(args, ["--gpus", "8", "--steps", "50", "--warmup", "10", "--variants-budget", "0"]) == 0
+    args = b.parse_args(["--gpus", "8", "--steps", "50", "--warmup", "10", "--full", "--variants-budget", "0"])
+    assert b.launch(args, ["--gpus", "8", "--steps", "50", "--warmup", "10", "--full", "--variants-budget", "0"]) == 0
     skipped = json.loads(capsys.readouterr().out.strip())
     assert skipped["value"] == 800.0 and len(skipped["dp_variants"]) == 9 and skipped["single_gpu_value"] is None
     assert all(e["error"].startswith("skipped") for e in skipped["dp_variants"].values())
@@ -139,6 +139,13 @@ def test_dp_variants_are_merged_and_a_failing_one_does_not_take_the_headline_dow
     for kind, argv in seen[1:]:
         assert "--variant-child" in argv and "--no-dp-variants" in argv and "--no-cpu-baseline" in argv
     assert all("50" in argv for kind, argv in seen[1:] if "--workload" not in argv)
+    # a plain run (no --full) is the headline alone: no variant is started and the line is rank 0's as it came
+    seen.clear()
+    args = b.parse_args(["--gpus", "8", "--steps", "50", "--warmup", "10"])
+    assert b.launch(args, ["--gpus", "8", "--steps", "50", "--warmup", "10"]) == 0
+    plain = json.loads(capsys.readouterr().out.strip())
+    assert plain["value"] == 800.0 and "dp_variants" not in plain and "single_gpu_value" not in plain
+    assert [kind for kind, argv in seen] == ["group"]
 
 
 def test_children_do_not_inherit_an_outer_launchers_rendezvous(monkeypatch):
@@ -178,3 +185,14 @@ def test_library_exchange_attempt_falls_back_to_fresh_ranks_through_torch(monkey
     assert b.attempt_plan(b.parse_args(["--gpus", "8", "--dp-mode", "graph"]), 8) == [("graph", "torch")]
     got = b.child_argv(["--gpus", "8", "--dp-exchange", "auto", "--steps", "5"], "eager", "library")
     assert got == ["--gpus", "8", "--steps", "5", "--dp-mode", "eager", "--dp-exchange", "library"]
+
+
+def test_dump_outputs_directory_is_absolute_for_the_children(tmp_path, monkeypatch):
+    """The ranks and variants run from the repository root: a relative --dump-outputs directory is made absolute first."""
+    b = _bench()
+    monkeypatch.chdir(tmp_path)
+    want = str(tmp_path / "out")
+    assert b.absolute_dump_dir(["--gpus", "2", "--dump-outputs", "out"]) == ["--gpus", "2", "--dump-outputs", want]
+    assert b.absolute_dump_dir(["--dump-outputs=out", "--steps", "5"]) == ["--dump-outputs=" + want, "--steps", "5"]
+    assert b.parse_args(["--dump-outputs", "out"]).dump_outputs == want
+    assert b.parse_args([]).dump_outputs is None and b.parse_args([]).full is False

@@ -1,13 +1,15 @@
 """The label files the reference HOLDS (data/train-labels-idx1-ubyte, data/t10k-labels-idx1-ubyte: with logs/trainLog.csv the
 only reference-held data on this path) as a committed fixture, tests/golden/reference_labels.json, written by
-tests/golden/make_label_fixture.py in the build container.  What they pin, on the CPU:
+tests/golden/make_label_fixture.py from the committed copies of those files, tests/golden/*-labels-idx1-ubyte.gz.  What they
+pin, on the CPU:
   * the IDX label format as MNISTTrainer reads it (MT:38-40, 49-52: big-endian magic 2049, count; MT:112-118: a byte per label)
-    -- `read_idx_labels` of the product's host side on the real files where the reference is present (the build container),
-    and on a file rebuilt from the fixture anywhere;
+    -- `read_idx_labels` of the product's host side on the real files (the committed copies, unpacked) and on a file rebuilt
+    from the fixture;
   * the label -> one-hot encoding (MT:112-118) of the oracle;
   * which rows of THOSE files the trainer's sampler draws first (NNT:143-168, Random(1) of NNT:42): the product's sampler
     (csrc/sampler.hip, host code) against the rows the fixture recorded from the oracle's, and the labels found there.
 The GPU half (one-hot upload, a 300-step trajectory on images labelled by these labels) is tests/test_reference_labels_gpu.py."""
+import gzip
 import json
 import os
 import struct
@@ -17,7 +19,7 @@ import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 FIXTURE = os.path.join(HERE, "golden", "reference_labels.json")
-REF_DATA = "/root/reference/data"
+REF_DATA = os.path.join(HERE, "golden")   # the reference's data/*-labels-idx1-ubyte, gzipped
 TRAIN_HISTOGRAM = [5923, 6742, 5958, 6131, 5842, 5421, 5918, 6265, 5851, 5949]   # SURVEY 8d; the judge's brief for round 4
 T10K_HISTOGRAM = [980, 1135, 1032, 1010, 982, 892, 958, 1028, 974, 1009]
 
@@ -47,10 +49,13 @@ def test_fixture_is_what_the_reference_files_say(fx):
     # (the five rows of logs/trainLog.csv are the other reference-held vectors: tests/golden/reference_train_log_rows.json)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_DATA), reason="the reference's files exist in the build container only")
-def test_product_reader_on_the_reference_files(gnn, fx):
+def test_product_reader_on_the_reference_files(gnn, fx, tmp_path):
     for key, name in (("train", "train-labels-idx1-ubyte"), ("t10k", "t10k-labels-idx1-ubyte")):
-        lab = gnn.read_idx_labels(os.path.join(REF_DATA, name))
+        with gzip.open(os.path.join(REF_DATA, name + ".gz")) as f:
+            raw = f.read()
+        assert len(raw) == fx[key]["file_bytes"]
+        (tmp_path / name).write_bytes(raw)
+        lab = gnn.read_idx_labels(tmp_path / name)
         d = fx[key]
         assert lab.dtype == np.uint8 and lab.size == d["n"]
         assert np.bincount(lab, minlength=10).tolist() == d["histogram"]
@@ -58,7 +63,7 @@ def test_product_reader_on_the_reference_files(gnn, fx):
         assert "%016x" % fnv1a64(lab.tobytes()) == d["payload_fnv1a64"]
         assert lab[d["first_sampler_rows"]].tolist() == d["labels_at_first_sampler_rows"]
         with pytest.raises(ValueError):        # an image reader on a label file: MT:39 asserts magic 2051
-            gnn.read_idx_images(os.path.join(REF_DATA, name))
+            gnn.read_idx_images(tmp_path / name)
 
 
 def test_product_reader_on_a_file_rebuilt_from_the_fixture(gnn, fx, tmp_path):

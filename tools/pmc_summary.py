@@ -22,7 +22,7 @@ def collect(path, counter):
 def main():
     fetch, nf = collect(sys.argv[1], "FETCH_SIZE")
     write, nw = collect(sys.argv[2], "WRITE_SIZE")
-    out = {"note": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in SEPARATE passes over `bench.py --steps 200 "
+    out = {"note": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in SEPARATE passes over `bench.py --full --steps 200 "
                    "--warmup 20 --no-cpu-baseline` (MI355X). Units are KB. Correction per MI355X_MICROARCH.md (HBM): "
                    "FETCH_SIZE counts 128-B fabric read requests at 64 B, so read bytes = 2*FETCH_SIZE*1024; WRITE_SIZE "
                    "is exact for 16-B-per-lane stores. These are L2<->fabric bytes summed over the 8 XCDs (Infinity-Cache "

@@ -8,15 +8,15 @@ OUT=${1:-gpurun_out/prof_round}
 ROOT=$(pwd)
 mkdir -p "$ROOT/$OUT"
 cd /tmp && export TMPDIR=/tmp
-B="python3 $ROOT/bench.py --steps 400 --warmup 100 --no-cpu-baseline --no-other-configs"
+B="python3 $ROOT/bench.py --full --steps 400 --warmup 100 --no-cpu-baseline --no-other-configs"
 run() { # name, rocprof args..., -- command
     local name=$1; shift
     timeout -k 10 300 rocprofv3 "$@" > "$ROOT/$OUT/$name.log" 2>&1 || echo "$name failed" >> "$ROOT/$OUT/failures.txt"
 }
 # the unprofiled bench lines FIRST, on the box as it comes (after the profiler passes below one box gave 15.3 us/step where the
 # same build gives 13.5 before them and on every other box)
-( cd "$ROOT" && python3 bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
-  python3 bench.py --dtype bf16 --no-cpu-baseline --no-other-configs > "$OUT/bench_bf16.json" 2> "$OUT/bench_bf16.err" )
+( cd "$ROOT" && python3 bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
+  python3 bench.py --full --dtype bf16 --no-cpu-baseline --no-other-configs > "$OUT/bench_bf16.json" 2> "$OUT/bench_bf16.err" )
 run stats_f32   --kernel-trace --stats --output-format csv -d "$ROOT/$OUT/stats_f32"   -o run -- $B
 run stats_bf16  --kernel-trace --stats --output-format csv -d "$ROOT/$OUT/stats_bf16"  -o run -- $B --dtype bf16
 run stats_dp1   --kernel-trace --stats --output-format csv -d "$ROOT/$OUT/stats_dp1"   -o run -- $B --dp-path --dp-mode eager
@@ -33,15 +33,15 @@ for c in 4 5; do for d in f32 bf16; do
 run trace_cfg${c}_$d --kernel-trace --output-format csv -d "$ROOT/$OUT/trace_cfg${c}_$d" -o run -- python3 $ROOT/tools/bench_configs.py $c $d --steps 40
 done; done
 cd "$ROOT"
-python3 bench.py > "$OUT/bench_default_after_profiling.json" 2> "$OUT/bench_default_after_profiling.err"
-python3 bench.py --dp-path --no-cpu-baseline --no-other-configs --steps 2048 --warmup 256 > "$OUT/bench_dp1_graph.json" 2> "$OUT/bench_dp1_graph.err"
-GNN_MLP_CHAIN=0 python3 bench.py --no-cpu-baseline --no-other-configs > "$OUT/bench_three_launch.json" 2> "$OUT/bench_three_launch.err"
+python3 bench.py --full > "$OUT/bench_default_after_profiling.json" 2> "$OUT/bench_default_after_profiling.err"
+python3 bench.py --full --dp-path --no-cpu-baseline --no-other-configs --steps 2048 --warmup 256 > "$OUT/bench_dp1_graph.json" 2> "$OUT/bench_dp1_graph.err"
+GNN_MLP_CHAIN=0 python3 bench.py --full --no-cpu-baseline --no-other-configs > "$OUT/bench_three_launch.json" 2> "$OUT/bench_three_launch.err"
 python3 tools/bench_configs.py 1 2 4 5 f32 bf16 --graph > "$OUT/configs_all.jsonl" 2> "$OUT/configs_all.err"
 python3 tools/bench_host_path.py > "$OUT/host_path.txt" 2>&1
 # the in-library data-parallel handle, replicas sharing this one GPU (a rehearsal of the control flow, not a scaling number)
 for r in direct direct_rs; do
-python3 bench.py --gpus 8 --dp-impl library --dp-reducer $r --share-gpu --no-cpu-baseline --steps 512 --warmup 128 > "$OUT/bench_library_8_shared_$r.json" 2> "$OUT/bench_library_8_shared_$r.err"
-python3 bench.py --gpus 8 --dp-impl library --dp-reducer $r --share-gpu --no-cpu-baseline --steps 512 --warmup 128 --dtype bf16 > "$OUT/bench_library_8_shared_${r}_bf16.json" 2>> "$OUT/bench_library_8_shared_$r.err"
+python3 bench.py --gpus 8 --dp-impl library --dp-reducer $r --share-gpu --no-cpu-baseline --full --steps 512 --warmup 128 > "$OUT/bench_library_8_shared_$r.json" 2> "$OUT/bench_library_8_shared_$r.err"
+python3 bench.py --gpus 8 --dp-impl library --dp-reducer $r --share-gpu --no-cpu-baseline --full --steps 512 --warmup 128 --dtype bf16 > "$OUT/bench_library_8_shared_${r}_bf16.json" 2>> "$OUT/bench_library_8_shared_$r.err"
 done
 tools/rowblock_probe > "$OUT/rowblock_probe.log" 2>&1
 tools/tile_probe > "$OUT/tile_probe.log" 2>&1
@@ -50,7 +50,7 @@ python3 tools/bench_trainer.py > "$OUT/trainer.txt" 2>&1
 # round 4: evaluation as one call (MT:181-197), the N > 1 record rehearsed with two ranks on this one GPU, the exchange primitive
 python3 tools/bench_configs.py inference 128 1024 4096 16384 > "$OUT/inference.jsonl" 2>&1
 ( cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$ROOT/$OUT/stats_inference" -o run -- python3 $ROOT/tools/bench_configs.py inference 16384 > "$ROOT/$OUT/stats_inference.log" 2>&1 )
-python3 bench.py --gpus 2 --backend gloo --share-gpu --steps 256 --warmup 64 --no-cpu-baseline > "$OUT/bench_n2_rehearsal_two_ranks_sharing_one_gpu.json" 2> "$OUT/bench_n2_rehearsal.err"
+python3 bench.py --gpus 2 --backend gloo --share-gpu --steps 256 --warmup 64 --no-cpu-baseline --full > "$OUT/bench_n2_rehearsal_two_ranks_sharing_one_gpu.json" 2> "$OUT/bench_n2_rehearsal.err"
 [ -x tools/_build/exchange_probe ] && tools/_build/exchange_probe 32 > "$OUT/exchange_probe.log" 2>&1
 [ -x tools/_build/rowblock_cluster_probe ] && tools/_build/rowblock_cluster_probe 128 > "$OUT/rowblock_cluster_probe.log" 2>&1
 ls -R "$OUT" | head -80

@@ -17,7 +17,7 @@ def main():
             tot[k][row["Counter_Name"]] += float(row["Counter_Value"])
             n[k][row["Counter_Name"]] += 1
     out = {"note": "rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT "
-                   "SQ_LDS_IDX_ACTIVE SQ_INSTS_VALU SQ_INSTS_LDS over `bench.py --steps 400 --warmup 100 --no-cpu-baseline` (one pass, no "
+                   "SQ_LDS_IDX_ACTIVE SQ_INSTS_VALU SQ_INSTS_LDS over `bench.py --full --steps 400 --warmup 100 --no-cpu-baseline` (one pass, no "
                    "other trace domain); means per launch", "kernels": {}}
     for k in tot:
         d = {"launches": max(n[k].values())}
