@@ -65,17 +65,6 @@ __host__ inline XcdTiling make_xcd_tiling(int tiles_m, int tiles_n) {
     return best;
 }
 
-#define GNN_STAMP_AT(ptr, i)                                                                  \
-    do {                                                                                      \
-        if (STAMP && threadIdx.x == 0) (ptr)[blockIdx.x * 8 + (i)] = __builtin_amdgcn_s_memtime(); \
-    } while (0)
-// s_memtime counts per-CU clocks with unrelated origins; the 100 MHz real-time counter is shared by
-// the whole device and is what block-to-block spans are measured with (slots 4 and 5)
-#define GNN_STAMP_REAL(ptr, i)                                                                \
-    do {                                                                                      \
-        if (STAMP && threadIdx.x == 0) (ptr)[blockIdx.x * 8 + (i)] = __builtin_amdgcn_s_memrealtime(); \
-    } while (0)
-
 // ------------------------------------------------------------------------------------------
 // fwd_first_kernel: C[M x N] = epi(A[M x K] . W[K x N]), A k-contiguous, W n-contiguous.
 // One 16x16 output tile per workgroup; NW waves split K in 16-wide chunks, partial tiles are
@@ -89,11 +78,10 @@ struct FwdFirstParams {
     int m_true, n_true;
     int act, apply_act;
     XcdTiling tiling;
-    unsigned long long *stamps; // STAMP builds only
     const int32_t *row_idx;     // optional: row m of A is dataset row row_idx[m] (sampled batches, NNT:143-158)
 };
 
-template <int NW, bool STAMP = false, int ACT = -1>
+template <int NW, int ACT = -1>
 __global__ __launch_bounds__(NW * 64) void fwd_first_kernel(FwdFirstParams p) {
     constexpr int MAXC = NW >= 8 ? 8 : NW >= 4 ? 13 : NW == 3 ? 17 : 25; // chunks whose loads are in flight at once (MAXC * (4+4) VGPRs)
     constexpr int RLD = 20; // row stride of a partial tile in LDS
@@ -111,8 +99,6 @@ __global__ __launch_bounds__(NW * 64) void fwd_first_kernel(FwdFirstParams p) {
     const float *arow = p.A + (size_t)a_row * p.lda + 4 * fq;
     const float *wcol = p.W + (size_t)(4 * fq) * p.ldw + n0 + fr;
 
-    GNN_STAMP_AT(p.stamps, 0);
-    GNN_STAMP_REAL(p.stamps, 4);
     f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
     for (int cb = c_begin; cb < c_end; cb += MAXC) {
         float4 a[MAXC];
@@ -148,12 +134,10 @@ __global__ __launch_bounds__(NW * 64) void fwd_first_kernel(FwdFirstParams p) {
         }
     }
     const f32x4 acc = acc0 + acc1;
-    GNN_STAMP_AT(p.stamps, 1);
     // partial tile, row-major: row = fq*4 + r, col = fr
 #pragma unroll
     for (int r = 0; r < 4; r++) red[(wave * 16 + fq * 4 + r) * RLD + fr] = acc[r];
     __syncthreads();
-    GNN_STAMP_AT(p.stamps, 2);
     if (t < 64) { // thread -> (row m = t/4, 4 columns): one 16-B store per lane
         const int m = t >> 2, q = t & 3;
         f32x4 s = {0.f, 0.f, 0.f, 0.f};
@@ -171,8 +155,6 @@ __global__ __launch_bounds__(NW * 64) void fwd_first_kernel(FwdFirstParams p) {
         }
         *reinterpret_cast<float4 *>(p.C + (size_t)(m0 + m) * p.ldc + n0 + q * 4) = o;
     }
-    GNN_STAMP_AT(p.stamps, 3);
-    GNN_STAMP_REAL(p.stamps, 5);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -195,15 +177,14 @@ struct GradParams {
     int n_layers;
     int K;                     // padded batch rows
     float step_over_b, momentum;
-    unsigned long long *stamps; // STAMP builds only
     const int32_t *row_idx;     // optional, layer 0 only: batch row k of A_0 is dataset row row_idx[k]
     int k_true;                 // live batch rows (rows past them are zeros when row_idx is given)
 };
 
-constexpr int GRAD_THREADS = 512; // default: 8 waves; 256 (4 waves, no K halves) for grids of > ~1000 tiles
-template <bool FUSED, bool STAMP = false, int NTHR = GRAD_THREADS>
-__global__ __launch_bounds__(NTHR) void grad_update_kernel(GradParams p) {
-    constexpr int KSPLIT = NTHR / 256;
+constexpr int GRAD_THREADS = 512; // 8 waves
+template <bool FUSED>
+__global__ __launch_bounds__(GRAD_THREADS) void grad_update_kernel(GradParams p) {
+    constexpr int NTHR = GRAD_THREADS, KSPLIT = NTHR / 256;
     constexpr int KC = 128, LDS_LD = 48; // row stride = 16 (mod 32) floats
     constexpr int CLD = 36;
     __shared__ __attribute__((aligned(16))) float As[KC * LDS_LD];
@@ -228,8 +209,6 @@ __global__ __launch_bounds__(NTHR) void grad_update_kernel(GradParams p) {
     const int er = (t >> 3) & 31, eq = t & 7;
     const bool e_ok = t < 256 && (m0 + er < L.M) && (n0 + eq * 4 < L.N);
     const size_t e_off = (size_t)(m0 + er) * L.ldd + n0 + eq * 4;
-    GNN_STAMP_AT(p.stamps, 0);
-    GNN_STAMP_REAL(p.stamps, 4);
     float4 w_old = make_float4(0.f, 0.f, 0.f, 0.f), v_old = w_old;
 
     f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
@@ -266,7 +245,6 @@ __global__ __launch_bounds__(NTHR) void grad_update_kernel(GradParams p) {
             *reinterpret_cast<float4 *>(&Ds[k * LDS_LD + q * 4]) = vd[i];
         }
         __syncthreads();
-        GNN_STAMP_AT(p.stamps, 1);
         const float *ap = &As[fq * LDS_LD + wm * 16 + fr];
         const float *dp = &Ds[fq * LDS_LD + wn * 16 + fr];
         // 32 k (8 MFMAs) per trip, the trip's 16 LDS reads issued before its first MFMA; a full
@@ -293,7 +271,6 @@ __global__ __launch_bounds__(NTHR) void grad_update_kernel(GradParams p) {
         }
     }
     const f32x4 acc = acc0 + acc1;
-    GNN_STAMP_AT(p.stamps, 2);
 #pragma unroll
     for (int r = 0; r < 4; r++) Cs[(kh * 32 + wm * 16 + fq * 4 + r) * CLD + wn * 16 + fr] = acc[r];
     __syncthreads();
@@ -316,8 +293,6 @@ __global__ __launch_bounds__(NTHR) void grad_update_kernel(GradParams p) {
             *reinterpret_cast<float4 *>(L.G + e_off) = gsum;
         }
     }
-    GNN_STAMP_AT(p.stamps, 3);
-    GNN_STAMP_REAL(p.stamps, 5);
 }
 
 // ------------------------------------------------------------------------------------------

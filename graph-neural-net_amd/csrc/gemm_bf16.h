@@ -26,18 +26,6 @@
 #pragma once
 #include "kernels.h"
 
-// tools/gemm_probe defines GNN_GEMM_BF16_STAMPS: wave 0 of workgroup (0, 0) adds up the cycles between the marks of the main loop
-#ifdef GNN_GEMM_BF16_STAMPS
-__device__ unsigned long long gnn_bf16_stamps[16];
-#define GNN_STAMP_DECL unsigned long long st_sum[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, st_prev = __builtin_readcyclecounter(); const unsigned long long st_begin = st_prev
-#define GNN_STAMP(i) do { asm volatile("" ::: "memory"); const unsigned long long st_now = __builtin_readcyclecounter(); st_sum[i] += st_now - st_prev; st_prev = st_now; } while (0)
-#define GNN_STAMP_FLUSH do { if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) { for (int i = 0; i < 9; i++) gnn_bf16_stamps[i] = st_sum[i]; gnn_bf16_stamps[9] = __builtin_readcyclecounter() - st_begin; } } while (0)
-#else
-#define GNN_STAMP_DECL
-#define GNN_STAMP(i)
-#define GNN_STAMP_FLUSH
-#endif
-
 namespace gnn {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -159,12 +147,10 @@ constexpr size_t gemm_bf16_lds_bytes() {
 }
 
 // WM: wave rows (waves are WM x 2, WM * 128 threads); WM = 4 puts eight waves on a tile (see gemm_f32_kernel)
-// (tools/gemm_probe only: NSTG_ = NSTG + 10 x ablation -- 1: no global loads inside the loop, 2: no MFMAs, 3: no LDS reads, 4: no LDS writes)
 // (the body: one BM x BN tile of product `p`, tile column bx, tile row by -- gemm_bf16_kernel's grid gives them, the grouped
 //  kernel below finds them from a flat workgroup number)
-template <int BM, int BN, bool A_KC, bool B_KC, int EPI, int NSTG_, int WM>
+template <int BM, int BN, bool A_KC, bool B_KC, int EPI, int NSTG, int WM>
 __device__ __forceinline__ void gemm_bf16_tile(const GemmBf16Params &p, const int bx, const int by) {
-    constexpr int NSTG = NSTG_ % 10, ABL = NSTG_ / 10;
     constexpr int NT = WM * 128;
     constexpr int BK = GemmBf16Depth<BM>::BK;
     constexpr int TM = BM / (WM * 16), TN = BN / 32; // 16x16 MFMA tiles per wave (waves are WM x 2)
@@ -256,7 +242,6 @@ __device__ __forceinline__ void gemm_bf16_tile(const GemmBf16Params &p, const in
         return (k & ~31) + 4 * g + (e & 3) + 16 * (e >> 2);
     };
     auto store_tiles = [&](const bf16x8 (&ra)[NA], const bf16x8 (&rb)[NB]) {
-        if constexpr (ABL == 4) { asm volatile("" ::"v"(ra[0]), "v"(rb[0])); return; }
 #pragma unroll
         for (int i = 0; i < NA; i++) {
             const int c = t + i * NT;
@@ -289,13 +274,6 @@ __device__ __forceinline__ void gemm_bf16_tile(const GemmBf16Params &p, const in
     // Fragments of the NEXT 32-wide k block are read while this block's MFMAs issue (as in gemm_f32_kernel): a bf16 block is
     // only TM*TN MFMAs of 16 cycles, far less than an LDS round trip, and with one workgroup per CU nothing else covers it.
     auto read_block = [&](int kk, bf16x8 (&a)[TM], bf16x8 (&b)[TN]) {
-        if constexpr (ABL == 3) {
-#pragma unroll
-            for (int i = 0; i < TM; i++) a[i] = ra0[0];
-#pragma unroll
-            for (int j = 0; j < TN; j++) b[j] = rb0[0];
-            return;
-        }
 #pragma unroll
         for (int i = 0; i < TM; i++)
             a[i] = A_KC ? frag_kc(As, wm * (TM * 16) + i * 16, kk) : frag_tr(As, LDTA, wm * (TM * 16) + i * 16, kk);
@@ -308,8 +286,7 @@ __device__ __forceinline__ void gemm_bf16_tile(const GemmBf16Params &p, const in
         for (int i = 0; i < TM; i++)
 #pragma unroll
             for (int j = 0; j < TN; j++)
-                if constexpr (ABL == 2) { acc[i][j][0] += (float)a[i][0]; acc[i][j][1] += (float)b[j][0]; }
-                else acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i], b[j], acc[i][j], 0, 0, 0);
+                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i], b[j], acc[i][j], 0, 0, 0);
     };
     constexpr int NBLK = BK / 32;
     constexpr bool DEEP = NSTG == 3 || NSTG == 4; // (NSTG 4: the two-barrier loop with the deep fragment prefetch)
@@ -387,33 +364,22 @@ __device__ __forceinline__ void gemm_bf16_tile(const GemmBf16Params &p, const in
                 }
             }
         } else if constexpr (NSTG >= 2) {
-            GNN_STAMP_DECL;
             load_tiles(0, ra0, rb0, inside);
             if (BK < p.K) load_tiles(BK, ra1, rb1, inside);
             for (int k0 = 0; k0 < p.K; k0 += 2 * BK) { // two tiles per trip so that the stages keep their names
-                GNN_STAMP(0);
                 store_tiles(ra0, rb0);
-                GNN_STAMP(1);
                 __syncthreads();
-                GNN_STAMP(2);
-                if (k0 + 2 * BK < p.K && ABL != 1) load_tiles(k0 + 2 * BK, ra0, rb0, inside);
+                if (k0 + 2 * BK < p.K) load_tiles(k0 + 2 * BK, ra0, rb0, inside);
                 multiply(k0);
-                GNN_STAMP(3);
                 __syncthreads();
-                GNN_STAMP(4);
                 if (k0 + BK < p.K) {
                     store_tiles(ra1, rb1);
-                    GNN_STAMP(5);
                     __syncthreads();
-                    GNN_STAMP(6);
-                    if (k0 + 3 * BK < p.K && ABL != 1) load_tiles(k0 + 3 * BK, ra1, rb1, inside);
+                    if (k0 + 3 * BK < p.K) load_tiles(k0 + 3 * BK, ra1, rb1, inside);
                     multiply(k0 + BK);
-                    GNN_STAMP(7);
                     __syncthreads();
-                    GNN_STAMP(8);
                 }
             }
-            GNN_STAMP_FLUSH;
         } else {
             load_tiles(0, ra0, rb0, inside);
             for (int k0 = 0; k0 < p.K; k0 += BK) {
@@ -432,10 +398,10 @@ __device__ __forceinline__ void gemm_bf16_tile(const GemmBf16Params &p, const in
     gemm_bf16_epilogue<TM, TN, EPI>(acc, p, reinterpret_cast<float *>(gemm_bf16_smem), m0, n0, wave, lane);
 }
 
-template <int BM, int BN, bool A_KC, bool B_KC, int EPI, int NSTG_ = 2, int WM = 2>
+template <int BM, int BN, bool A_KC, bool B_KC, int EPI, int NSTG = 2, int WM = 2>
 __global__ __launch_bounds__(WM * 128) void gemm_bf16_kernel(GNN_GEMM_HEAD_PARAMS(__bf16), GemmBf16Params p) {
     GNN_GEMM_TAKE_HEAD(p);
-    gemm_bf16_tile<BM, BN, A_KC, B_KC, EPI, NSTG_, WM>(p, blockIdx.x, blockIdx.y);
+    gemm_bf16_tile<BM, BN, A_KC, B_KC, EPI, NSTG, WM>(p, blockIdx.x, blockIdx.y);
 }
 
 // SEVERAL products of one form in ONE launch: the gradient (+ update) products of all layers of a net whose products are each
@@ -449,7 +415,7 @@ struct GemmBf16Group {
     int tiles_x[GNN_GEMM_GROUP_MAX];
     int n;
 };
-template <int BM, int BN, bool A_KC, bool B_KC, int EPI, int NSTG_ = 2, int WM = 2>
+template <int BM, int BN, bool A_KC, bool B_KC, int EPI, int NSTG = 2, int WM = 2>
 __global__ __launch_bounds__(WM * 128) void gemm_bf16_group_kernel(GemmBf16Group g) {
     const int w = blockIdx.x;
     GemmBf16Params p = g.p[0]; // (selected with scalar moves: an index into the argument block would put the array in scratch)
@@ -458,7 +424,7 @@ __global__ __launch_bounds__(WM * 128) void gemm_bf16_group_kernel(GemmBf16Group
     for (int i = 1; i < GNN_GEMM_GROUP_MAX; i++)
         if (i < g.n && w >= g.first[i]) { p = g.p[i]; first = g.first[i]; tiles_x = g.tiles_x[i]; }
     const int local = w - first;
-    gemm_bf16_tile<BM, BN, A_KC, B_KC, EPI, NSTG_, WM>(p, local % tiles_x, local / tiles_x);
+    gemm_bf16_tile<BM, BN, A_KC, B_KC, EPI, NSTG, WM>(p, local % tiles_x, local / tiles_x);
 }
 
 // f32 -> bf16 (RNE) over a flat buffer: the shadow of W after set_weights / init / load, dataset rows, ...

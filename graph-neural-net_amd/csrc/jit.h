@@ -39,7 +39,7 @@ inline std::string shape_list(const int *dims, int L) {
     return s;
 }
 
-// Compiles middle4_kernel<StaticShape<dims...>, act, outk, backward, false, slabs> for gfx950:
+// Compiles middle4_kernel<StaticShape<dims...>, act, outk, backward, slabs> for gfx950:
 // (false, false), (true, false) and, when `with_slabs`, (true, true).
 // Returns the code object (empty on failure; *log holds the compiler output).
 // bf16: ONE kernel, (true, true, BF16 = true) -- the training kernel of the two-launch path in GNN_DTYPE_BF16 -- in slot 2.
@@ -50,7 +50,7 @@ inline std::vector<char> compile_middle4(const int *dims, int L, int act, int ou
     std::string expr[3];
     for (int b = b_first; b < n_fn; b++)
         expr[b] = "gnn::middle4_kernel<" + shape + ", " + std::to_string(act) + ", " + std::to_string(outk) + ", " +
-                  (b ? "true" : "false") + ", false, " + (b == 2 ? "true" : "false") + ", " + (bf16 ? "true" : "false") + ">";
+                  (b ? "true" : "false") + ", " + (b == 2 ? "true" : "false") + ", " + (bf16 ? "true" : "false") + ">";
     const std::string src = "#include \"middle4_kernel.h\"\n";
     const char *hdr_src[] = {kEmbedded_kernels_h, kEmbedded_fused_kernels_h, kEmbedded_middle4_kernel_h};
     const char *hdr_name[] = {"kernels.h", "fused_kernels.h", "middle4_kernel.h"};
@@ -132,7 +132,7 @@ inline const Specialised *get_rowblock(int device, const int *dims, int L, int a
     if (it != cache.end()) return it->second.fn[0] ? &it->second : nullptr;
     Specialised &sp = cache[key];
     sp.n_fn = 1;
-    const std::string expr = "gnn::rowblock_kernel<gnn::RbStaticShape<" + shape_list(dims, L) + ">, " + std::to_string(act) + ", " + std::to_string(outk) + ", false, 0, " + (bf16 ? "true" : "false") + ">";
+    const std::string expr = "gnn::rowblock_kernel<gnn::RbStaticShape<" + shape_list(dims, L) + ">, " + std::to_string(act) + ", " + std::to_string(outk) + ", " + (bf16 ? "true" : "false") + ">";
     const std::string src = "#include \"rowblock_kernel.h\"\n";
     const char *hdr_src[] = {kEmbedded_kernels_h, kEmbedded_fused_kernels_h, kEmbedded_middle4_kernel_h, kEmbedded_rowblock_kernel_h};
     const char *hdr_name[] = {"kernels.h", "fused_kernels.h", "middle4_kernel.h", "rowblock_kernel.h"};

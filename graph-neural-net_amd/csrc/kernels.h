@@ -251,10 +251,6 @@ __global__ __launch_bounds__(WM * 128) void gemm_f32_kernel(GNN_GEMM_HEAD_PARAMS
         }
     };
     auto store_tiles = [&](const float4 (&ra)[NA], const float4 (&rb)[NB]) {
-#ifdef GNN_F32_NO_LDS_WRITES // (tools/gemm_probe, timing only: what the write phase of the loop costs)
-        asm volatile("" ::"v"(ra[0].x), "v"(rb[0].x));
-        return;
-#endif
 #pragma unroll
         for (int i = 0; i < NA; i++) {
             const int idx = t + i * NT;

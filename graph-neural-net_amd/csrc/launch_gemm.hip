@@ -117,7 +117,7 @@ void forward(gnn_mlp *h, const float *a0, int B, int first_l, bool stop_before_l
             f.m_true = p.m_true; f.n_true = p.n_true;
             f.act = 0; f.apply_act = 0;
             f.tiling = make_xcd_tiling(f.M / 16, f.N / 16);
-            launch_timed(h, -1, fwd_first_kernel<FIRST_NW, false, -1>, dim3(f.tiling.blocks()), dim3(FIRST_NW * 64), 0, f);
+            launch_timed(h, -1, fwd_first_kernel<FIRST_NW, -1>, dim3(f.tiling.blocks()), dim3(FIRST_NW * 64), 0, f);
         } else {
             p.C = h->logits; p.ldc = h->ld[l];
             launch_gemm<true, false, EPI_STORE>(h, l == 1 ? GNN_K_FWD_GEMM0 : -1, p);
@@ -230,20 +230,20 @@ void launch_fwd_first(gnn_mlp *h, const float *a0, int B) {
     if (f.K / 16 <= 4 * 13) {
         const dim3 fb(4 * 64);
         switch (h->inner_act) {
-        case 0: launch_timed(h, GNN_K_FWD_GEMM0, fwd_first_kernel<4, false, 0>, fg, fb, 0, f); break;
-        case 1: launch_timed(h, GNN_K_FWD_GEMM0, fwd_first_kernel<4, false, 1>, fg, fb, 0, f); break;
-        case 2: launch_timed(h, GNN_K_FWD_GEMM0, fwd_first_kernel<4, false, 2>, fg, fb, 0, f); break;
-        case 3: launch_timed(h, GNN_K_FWD_GEMM0, fwd_first_kernel<4, false, 3>, fg, fb, 0, f); break;
-        default: launch_timed(h, GNN_K_FWD_GEMM0, fwd_first_kernel<4, false, 4>, fg, fb, 0, f); break;
+        case 0: launch_timed(h, GNN_K_FWD_GEMM0, fwd_first_kernel<4, 0>, fg, fb, 0, f); break;
+        case 1: launch_timed(h, GNN_K_FWD_GEMM0, fwd_first_kernel<4, 1>, fg, fb, 0, f); break;
+        case 2: launch_timed(h, GNN_K_FWD_GEMM0, fwd_first_kernel<4, 2>, fg, fb, 0, f); break;
+        case 3: launch_timed(h, GNN_K_FWD_GEMM0, fwd_first_kernel<4, 3>, fg, fb, 0, f); break;
+        default: launch_timed(h, GNN_K_FWD_GEMM0, fwd_first_kernel<4, 4>, fg, fb, 0, f); break;
         }
     } else {
         const dim3 fb(FIRST_NW * 64);
         switch (h->inner_act) {
-        case 0: launch_timed(h, GNN_K_FWD_GEMM0, fwd_first_kernel<FIRST_NW, false, 0>, fg, fb, 0, f); break;
-        case 1: launch_timed(h, GNN_K_FWD_GEMM0, fwd_first_kernel<FIRST_NW, false, 1>, fg, fb, 0, f); break;
-        case 2: launch_timed(h, GNN_K_FWD_GEMM0, fwd_first_kernel<FIRST_NW, false, 2>, fg, fb, 0, f); break;
-        case 3: launch_timed(h, GNN_K_FWD_GEMM0, fwd_first_kernel<FIRST_NW, false, 3>, fg, fb, 0, f); break;
-        default: launch_timed(h, GNN_K_FWD_GEMM0, fwd_first_kernel<FIRST_NW, false, 4>, fg, fb, 0, f); break;
+        case 0: launch_timed(h, GNN_K_FWD_GEMM0, fwd_first_kernel<FIRST_NW, 0>, fg, fb, 0, f); break;
+        case 1: launch_timed(h, GNN_K_FWD_GEMM0, fwd_first_kernel<FIRST_NW, 1>, fg, fb, 0, f); break;
+        case 2: launch_timed(h, GNN_K_FWD_GEMM0, fwd_first_kernel<FIRST_NW, 2>, fg, fb, 0, f); break;
+        case 3: launch_timed(h, GNN_K_FWD_GEMM0, fwd_first_kernel<FIRST_NW, 3>, fg, fb, 0, f); break;
+        default: launch_timed(h, GNN_K_FWD_GEMM0, fwd_first_kernel<FIRST_NW, 4>, fg, fb, 0, f); break;
         }
     }
 }

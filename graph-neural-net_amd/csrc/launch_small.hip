@@ -31,8 +31,8 @@ const void *mid4_function(const gnn_mlp *h, int variant) {
     if (which >= 0)
         return h->out_kind == GNN_OUT_SOFTMAX_CE ? mid4_static_table<0>(which, h->inner_act, variant) : mid4_static_general(which, h->inner_act, variant);
     // runtime extents: layer count templated (3..6, else generic), activation read from the arguments
-#define GNN_M4RO(NL, OK) (variant == 3 ? reinterpret_cast<const void *>(&middle4_kernel<RuntimeShape<NL>, -1, OK, true, false, true, true>) \
-                          : variant == 2 ? reinterpret_cast<const void *>(&middle4_kernel<RuntimeShape<NL>, -1, OK, true, false, true>) \
+#define GNN_M4RO(NL, OK) (variant == 3 ? reinterpret_cast<const void *>(&middle4_kernel<RuntimeShape<NL>, -1, OK, true, true, true>) \
+                          : variant == 2 ? reinterpret_cast<const void *>(&middle4_kernel<RuntimeShape<NL>, -1, OK, true, true>) \
                           : variant == 1 ? reinterpret_cast<const void *>(&middle4_kernel<RuntimeShape<NL>, -1, OK, true>)           \
                                          : reinterpret_cast<const void *>(&middle4_kernel<RuntimeShape<NL>, -1, OK, false>))
 #define GNN_M4R(NL) (h->out_kind == GNN_OUT_SOFTMAX_CE ? GNN_M4RO(NL, 0) : GNN_M4RO(NL, 1))
@@ -79,8 +79,8 @@ void plan_mid4(gnn_mlp *h) {
 
 // ---- rowblock_kernel plan -----------------------------------------------------------------------
 template <int NL, bool BF> const void *rb_fn_runtime(int out_kind) {
-    return out_kind == GNN_OUT_SOFTMAX_CE ? reinterpret_cast<const void *>(&rowblock_kernel<RbRuntimeShape<NL>, -1, 0, false, 0, BF>)
-                                          : reinterpret_cast<const void *>(&rowblock_kernel<RbRuntimeShape<NL>, -1, 1, false, 0, BF>);
+    return out_kind == GNN_OUT_SOFTMAX_CE ? reinterpret_cast<const void *>(&rowblock_kernel<RbRuntimeShape<NL>, -1, 0, BF>)
+                                          : reinterpret_cast<const void *>(&rowblock_kernel<RbRuntimeShape<NL>, -1, 1, BF>);
 }
 
 void plan_rowblock(gnn_mlp *h) {

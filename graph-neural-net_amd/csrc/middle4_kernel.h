@@ -145,7 +145,6 @@ struct Mid4Params {
     float *prob; float *loss; int32_t *label;
     int B;
     int inner_act, last_act;     // inner_act is read only by kernels built with ACT = -1
-    unsigned long long *stamps;  // STAMP builds only
     const int32_t *row_idx;      // optional: expected row of batch row r is Y row row_idx[r] (sampled batches)
     // SLABS kernels: A_1 = f(sum of the K slabs of the first-layer sums) instead of reading act[1];
     // slab s of batch row b at slabs[(s * slab_rows + b) * ld[1]] (tile_step_kernel.h)
@@ -218,11 +217,6 @@ __device__ __forceinline__ void row16_argmax(float &v, int &ix) {
 #undef GNN_ARGMAX_STEP
 }
 
-#define GNN_STAMP4(i)                                                                             \
-    do {                                                                                          \
-        if (STAMP && threadIdx.x == 0) p.stamps[blockIdx.x * 16 + (i)] = __builtin_amdgcn_s_memtime(); \
-    } while (0)
-
 // partial[4][gw] (this wave's K part) = A_img[4 x Kpart] . B for column group n0..n0+63
 //   TRANS = false: B[k][n] = Wimg[k*ldw + n]   (forward:  n = neuron of the layer being produced)
 //   TRANS = true : B[k][n] = Wimg[n*ldw + k]   (backward: n = neuron of the layer receiving delta)
@@ -294,7 +288,7 @@ __device__ __forceinline__ void rowblock_product(const float *A_img, int lda, co
 __device__ __forceinline__ f32x4 m4_load16(const float *base, unsigned off) {
     return *reinterpret_cast<const f32x4 *>(reinterpret_cast<const char *>(base) + (size_t)(off * 4u));
 }
-template <int NL, int ACT_T, int OUTK, bool BACKWARD, bool STAMP, int NSLOT, int NS, bool BF = false, int NSLOT8 = 0, int SGV = 0>
+template <int NL, int ACT_T, int OUTK, bool BACKWARD, int NSLOT, int NS, bool BF = false, int NSLOT8 = 0, int SGV = 0>
 __device__ __forceinline__ void middle4_body(const Mid4Plan &m, Mid4Params &p) {
     const int ACT = (ACT_T >= 0) ? ACT_T : p.inner_act;
     auto opv = [](float x) { return BF ? bf16_value(x) : x; };  // the value an operand image holds
@@ -304,10 +298,6 @@ __device__ __forceinline__ void middle4_body(const Mid4Plan &m, Mid4Params &p) {
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6); // provably wave-uniform: scalar branches
     const int row0 = blockIdx.x * 4;
     const int L = (NL > 0) ? NL : m.L, Lm = L - 1;
-    // STAMP builds run the body twice and stamp the second (warm) pass into the next record
-    for (int pass = 0; pass < (STAMP ? 2 : 1); pass++) {
-    if (STAMP && pass == 1) { __syncthreads(); p.stamps += 16 * gridDim.x; }
-    GNN_STAMP4(0);
 
     // ---- phase 0: everything this block reads from memory, issued before anything waits ----
     // A_1 rows and expected rows: one float4 per thread (4*ld/4 <= 1024 floats4 since kr <= 1024),
@@ -596,7 +586,6 @@ __device__ __forceinline__ void middle4_body(const Mid4Plan &m, Mid4Params &p) {
         }
         __syncthreads();
     }
-    GNN_STAMP4(1);
 
     constexpr bool IS_STATIC = NSLOT > 0;
 
@@ -643,9 +632,7 @@ __device__ __forceinline__ void middle4_body(const Mid4Plan &m, Mid4Params &p) {
             }
             __syncthreads();
         }
-        GNN_STAMP4(4 + l);
     }
-    GNN_STAMP4(2);
 
     // ---- output layer: wave 0, one DPP row of 16 lanes per batch row ----
     if (rowtail) {
@@ -864,9 +851,8 @@ __device__ __forceinline__ void middle4_body(const Mid4Plan &m, Mid4Params &p) {
             if (p.label) p.label[row] = lrow ? best : -1;
         }
     }
-    if (!BACKWARD) { if (STAMP) continue; return; }
+    if (!BACKWARD) return;
     __syncthreads();
-    GNN_STAMP4(3);
 
     // ---- backward data: delta_l = (delta_{l+1} . W_l^T) * f'(z_l), l = L-2 .. 1 (SCE:262-278) ----
 #pragma unroll
@@ -906,15 +892,12 @@ __device__ __forceinline__ void middle4_body(const Mid4Plan &m, Mid4Params &p) {
             }
         }
         __syncthreads();
-        GNN_STAMP4(10 + l);
     }
-    GNN_STAMP4(4);
-    } // pass
 }
 
 // SLABS: A_1 comes as K slabs from tile_step_kernel (64 input neurons per slab) instead of from act[1]
 // BF16 : GNN_DTYPE_BF16 (see middle4_body); built only as the training kernel of the two-launch path (BACKWARD, SLABS)
-template <class SH, int ACT, int OUTK, bool BACKWARD, bool STAMP = false, bool SLABS = false, bool BF16 = false>
+template <class SH, int ACT, int OUTK, bool BACKWARD, bool SLABS = false, bool BF16 = false>
 __global__ __launch_bounds__(1024) void middle4_kernel(Mid4Params p) {
     static_assert(!BF16 || (BACKWARD && SLABS), "the bf16 row-block kernel exists for the two-launch training path only");
     if constexpr (SH::is_static) {
@@ -923,9 +906,9 @@ __global__ __launch_bounds__(1024) void middle4_kernel(Mid4Params p) {
         constexpr Mid4Plan m = SH::template make<BF16>();
         constexpr int ns = SLABS ? (m.ld[0] + 63) / 64 : 0;
         static_assert(ns <= MID4_MAX_SLABS, "too many first-layer slabs for the register-resident sum");
-        middle4_body<SH::kL, ACT, OUTK, BACKWARD, STAMP, m.st_total, ns, BF16, m.st8_total, (ns > 0 ? m.sgrp : 0)>(m, p);
+        middle4_body<SH::kL, ACT, OUTK, BACKWARD, m.st_total, ns, BF16, m.st8_total, (ns > 0 ? m.sgrp : 0)>(m, p);
     } else {
-        middle4_body<SH::kL, ACT, OUTK, BACKWARD, STAMP, 0, SLABS ? -1 : 0, BF16, 0>(p.plan, p);
+        middle4_body<SH::kL, ACT, OUTK, BACKWARD, 0, SLABS ? -1 : 0, BF16, 0>(p.plan, p);
     }
 }
 

@@ -129,7 +129,6 @@ struct RbParams {
     // product with plain addressing too, and the copy is this batch's gradient operand one step later (plan.hip, chain_gradient).
     float *xcopy; __bf16 *xcopyb; const float *X; const __bf16 *Xb; int ldx;
     const int32_t *copy_idx;
-    unsigned long long *stamps;  // STAMP builds only: 16 slots per workgroup
     // bf16 kernels (BF): the bf16 shadow of W_l and the bf16 outputs the tile kernel reads, as in Mid4Params
     const __bf16 *Wb[MAX_LAYERS];
     __bf16 *actb[MAX_LAYERS];
@@ -163,17 +162,6 @@ template <int NL> struct RbRuntimeShape {
     static constexpr int kL = NL;
 };
 
-#define GNN_RB_STAMP(i)                                                                                  \
-    do {                                                                                                 \
-        if (STAMP && threadIdx.x == 0) p.stamps[blockIdx.x * 16 + (i)] = __builtin_amdgcn_s_memtime();   \
-    } while (0)
-
-// per-wave stamps (STAMP builds): region r, 16 slots per workgroup behind the first 16 * gridDim.x
-#define GNN_RB_WSTAMP(r)                                                                                                         \
-    do {                                                                                                                         \
-        if (STAMP && lane == 0) p.stamps[(size_t)(16 * gridDim.x) * (1 + (r)) + blockIdx.x * 16 + wave] = __builtin_amdgcn_s_memtime(); \
-    } while (0)
-
 // x + (x of the lane 32 away): both halves of the wave end up with the sum.
 // (The two results are copied to scalars before they are reinterpreted: `__builtin_bit_cast(float, r[1])` on the builtin's
 //  vector result read element 0 twice with hipcc 7.2 -- every sum came out as 2 x one half.)
@@ -193,7 +181,7 @@ __device__ __forceinline__ float rb_sum16(float x) {
 }
 
 // NL > 0: layer count fixed at compile time; IS_STATIC: `m` is a compile-time constant (every extent folds)
-template <int NL, bool IS_STATIC, int ACT_T, int OUTK, bool STAMP, int NSV, int UPW1, int TUNE, bool BF>
+template <int NL, bool IS_STATIC, int ACT_T, int OUTK, int NSV, int UPW1, bool BF>
 __device__ __forceinline__ void rowblock_body(const RbPlan &m, RbParams &p) {
     const int ACT = (ACT_T >= 0) ? ACT_T : p.inner_act;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -209,7 +197,6 @@ __device__ __forceinline__ void rowblock_body(const RbPlan &m, RbParams &p) {
     // operand images, f' kept from the UNROUNDED activation -- on the same exact-f32 MFMA, outputs for the tile kernel in
     // bf16: middle4_kernel<.., BF16>'s arithmetic in this kernel's schedule.
     auto opv = [](float x) { return BF ? bf16_value(x) : x; };
-    GNN_RB_STAMP(0);
 
     // ---- phase 0 / 1: loads, and A_1 = f(sum of the slabs, slab order) ------------------------------------------------
     // What bounds this kernel is the CU's vector-memory pipe: it takes a wave-wide 16-B load in 16 cycles WHATEVER its
@@ -225,10 +212,8 @@ __device__ __forceinline__ void rowblock_body(const RbPlan &m, RbParams &p) {
     // (Re-measured after the head arguments moved into SGPRs -- the first loads now issue ~500 cycles earlier and the best order
     //  changed with it: the slabs first and ONE weight unit ahead, 6.22 us per launch; two units ahead 6.30; the weights in front of the
     //  slabs, the order of the builds before, 6.30 / 6.50 with one / two units; three units 7.44.  tools/rowblock_probe 128 1.)
-    constexpr int RB_PF = (TUNE & 0x600) ? ((TUNE >> 9) & 3) : 2; // weight units requested ahead of the one being multiplied
-    constexpr int PF0 = (TUNE & 7) ? (TUNE & 7) : 1; // units requested before A_1 is formed
-    constexpr bool W_FIRST = (TUNE & 8) != 0;      // (probe) the first weight units in FRONT of the slabs in every wave's queue
-    constexpr int PF1 = (TUNE & 0x800) ? PF0 + RB_PF : PF0; // (probe) units requested by the time of the A_1 barrier: the product's first RB_PF units right in front of it
+    constexpr int RB_PF = 2; // weight units requested ahead of the one being multiplied
+    constexpr int PF0 = 1;   // units requested before A_1 is formed
     // (the row index of a sampled batch's expected row is a DEPENDENT load: issued first)
     const int qy = m.ld[Lm] >> 2; // 4
     const int y_e = RB_NT - 1 - t, y_r = y_e / qy, y_q = y_e - y_r * qy; // the expected rows: the LAST threads
@@ -255,15 +240,13 @@ __device__ __forceinline__ void rowblock_body(const RbPlan &m, RbParams &p) {
 #pragma unroll
         for (int tt = 0; tt < 4; tt++) {
             const int k = 8 * u + 4 * hq + tt;
-            if (TUNE & (1 << 20)) w1[UPW1 > 0 ? uu : 0][tt] = (f32x4){0.01f * (float)k, 0.f, 0.02f, 0.f}; // (probe: what the weight stream costs -- no loads, wrong results)
-            else w1[UPW1 > 0 ? uu : 0][tt] = rb_load_w4<BF>(p.W[1], p.Wb[1], (unsigned)(k * m.ld[2] + colc_1));
+            w1[UPW1 > 0 ? uu : 0][tt] = rb_load_w4<BF>(p.W[1], p.Wb[1], (unsigned)(k * m.ld[2] + colc_1));
         }
     };
     // The copy of a wave's weight rows to the LDS image (for the backward product) costs the LDS store path 13 cycles per
     // 16-B write, 160 writes in all.  The waves whose threads sum the K slices afterwards (the first ceil(4 N / 4 / 64) of
     // them) do it between their MFMAs; the others wait until THEY are idle -- the slice sum -- so that neither the
     // product nor the row tail (whose LDS reads queued behind these writes when they ran beside it) pays for it.
-    constexpr bool DEFER = (TUNE & 16) == 0;
     constexpr int n_sum_waves = 4; // the row-tail waves copy between their MFMAs, waves 4..7 while the row tail runs
     int col_1 = 0;
     auto to_image_1 = [&](int uu) { // the rows this wave holds of unit uu, for the backward product
@@ -284,19 +267,12 @@ __device__ __forceinline__ void rowblock_body(const RbPlan &m, RbParams &p) {
         colc_1 = col_1 < m.ld[2] ? col_1 : m.ld[2] - 4;
         ulast_1 = U - 1;
     }
-    if constexpr (UPW1 > 0 && W_FIRST) {
-#pragma unroll
-        for (int uu = 0; uu < UPW1; uu++)
-            if (uu < PF0) load_unit_1(uu);
-        __builtin_amdgcn_sched_barrier(0);
-    }
     // the first-layer K slabs: one float4 of the four A_1 rows per thread, all slabs of it; slab order; then f.
     // Rows past the batch and columns past d_1 are zeros (f(0) != 0 for the sigmoid).
     const int q1 = m.ld[1] >> 2;
     f32x4 a1v = {0.f, 0.f, 0.f, 0.f}; // this thread's float4 of A_1 and where the tile kernel reads it (stored below, see there)
     unsigned a1_goff = 0xffffffffu;
     if (wave * 64 < 4 * q1) { // (wave-uniform)
-        if (TUNE & 64) { if (wave >= 4) __builtin_amdgcn_s_setprio(3); else __builtin_amdgcn_s_setprio(2); } // the slab waves over the others; the younger one of a SIMD first
         const bool a1_on = t < 4 * q1;
         const int a1_r = IS_STATIC ? t / q1 : (int)(((unsigned)t * (((1u << 22) + q1 - 1) / q1)) >> 22), a1_q = t - a1_r * q1;
         const unsigned zoff = a1_on ? (unsigned)(row0 + a1_r) * (unsigned)m.ld[1] + (unsigned)(a1_q * 4) : 0u;
@@ -305,15 +281,12 @@ __device__ __forceinline__ void rowblock_body(const RbPlan &m, RbParams &p) {
 #pragma unroll
         for (int i = 0; i < NSV; i++) {
             const unsigned o = zoff + (a1_on ? (unsigned)i * sstride : 0u);
-            if ((TUNE & (1 << 21)) && i > 0) zs[i] = (f32x4){0.001f * (float)i, 0.f, 0.f, 0.f}; // (probe: what twelve of the thirteen slab loads cost)
-            else zs[i] = m4_load16(p.slabs, i < m.ns ? o : 0u); // (runtime shapes: the slots past n_slabs re-read offset 0 and are not summed)
+            zs[i] = m4_load16(p.slabs, i < m.ns ? o : 0u); // (runtime shapes: the slots past n_slabs re-read offset 0 and are not summed)
         }
-        GNN_RB_STAMP(6); // this wave's phase-0 loads issued
         f32x4 z = zs[0];
 #pragma unroll
         for (int i = 1; i < NSV; i++)
             if (i < m.ns) z += zs[i];
-        if (STAMP) { asm volatile("" : "+v"(z)); GNN_RB_STAMP(7); } // this wave's slabs have landed
         const bool lrow = row0 + a1_r < p.B;
         f32x4 a;
 #pragma unroll
@@ -329,9 +302,8 @@ __device__ __forceinline__ void rowblock_body(const RbPlan &m, RbParams &p) {
             a1v = a;
             a1_goff = (unsigned)(row0 + a1_r) * (unsigned)m.ld[1] + (unsigned)(a1_q * 4);
         }
-        if (TUNE & 64) __builtin_amdgcn_s_setprio(0);
     }
-    if constexpr (UPW1 > 0 && !W_FIRST) {
+    if constexpr (UPW1 > 0) {
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int uu = 0; uu < UPW1; uu++)
@@ -345,22 +317,14 @@ __device__ __forceinline__ void rowblock_body(const RbPlan &m, RbParams &p) {
     if (Lm < 3 && y_on) *reinterpret_cast<f32x4 *>(smem + m.off_y + y_r * m.ld[Lm] + y_q * 4) = yv; // (no register product in front of the row tail)
     // the weight units requested in phase 0 have landed in front of the slabs (or this wave has no slabs and nothing else to
     // do until A_1 exists): their rows go to the LDS image NOW, in time the wave would spend waiting at the barrier
-    constexpr bool EARLY_IMG = (TUNE & 128) == 0;
     // The waves that sum slabs do not wait for their first weight unit in front of the barrier: no early copy for them (the
     // unit's rows go to the image inside the product like the others'), and A_1's store moves behind the product so that the
-    // unit's wait does not stand behind the store's round trip (6.26 -> 6.19 us; probe bit 0x1000 = every wave copies early)
-    constexpr bool SLAB_NOWAIT = (TUNE & 0x1000) == 0;
-    const bool early_here = !SLAB_NOWAIT || wave * 64 >= 4 * q1; // (wave-uniform)
-    if (EARLY_IMG && early_here && UPW1 > 0 && Lm >= 3) {
+    // unit's wait does not stand behind the store's round trip (6.26 -> 6.19 us against every wave copying early)
+    const bool early_here = wave * 64 >= 4 * q1; // (wave-uniform)
+    if (early_here && UPW1 > 0 && Lm >= 3) {
 #pragma unroll
         for (int uu = 0; uu < UPW1; uu++)
             if (uu < PF0 && uu < nu_1) to_image_1(uu);
-    }
-    if constexpr (UPW1 > 0 && PF1 > PF0) {
-#pragma unroll
-        for (int uu = PF0; uu < UPW1; uu++)
-            if (uu < PF1) load_unit_1(uu);
-        __builtin_amdgcn_sched_barrier(0);
     }
     // A_1 for the tile kernel: stored LAST.  The memory counter counts stores too, and the copies above wait for "all but
     // the youngest request" (what a wave without slabs needs): with the store in front of them the slab waves sat out its
@@ -371,10 +335,8 @@ __device__ __forceinline__ void rowblock_body(const RbPlan &m, RbParams &p) {
             else *reinterpret_cast<f32x4 *>(reinterpret_cast<char *>(p.act[1]) + (size_t)(a1_goff * 4u)) = a1v;
         }
     };
-    if (!SLAB_NOWAIT || !(UPW1 > 0 && Lm >= 3)) store_a1();
-    GNN_RB_WSTAMP(0); // this wave at the A_1 barrier
+    if (!(UPW1 > 0 && Lm >= 3)) store_a1();
     __syncthreads();
-    GNN_RB_STAMP(1);
 
     // The row tail's operands that do not depend on the activations -- the last weight image, once in the logits' layout
     // (lane (kg, q): rows kg + 16 i, columns 4q..) and once by row (lanes n and n + 64) for delta_{L-2} -- are read by the tail
@@ -434,16 +396,15 @@ __device__ __forceinline__ void rowblock_body(const RbPlan &m, RbParams &p) {
             f32x4 av1[UPW1 > 0 ? UPW1 : 1];
 #pragma unroll
             for (int uu = 0; uu < UPW1; uu++) av1[uu] = *reinterpret_cast<const f32x4 *>(arow + 8 * (u0 + (uu < nu ? uu : 0)));
-            if (STAMP) { asm volatile("" : "+v"(av1[UPW1 > 0 ? UPW1 - 1 : 0])); GNN_RB_WSTAMP(5); } // A operands here
             if (l + 1 == Lm - 1 && wave < 4) load_tail_weights(); // (wave-uniform; see there: LDS has nothing else to do here)
             // software pipeline over the wave's units: request unit uu + RB_PF, multiply unit uu, copy its rows to the LDS
             // image for the backward product (13 cycles of the LDS store path per write, under the matrix pipe's 128 per unit)
 #pragma unroll
             for (int uu = 0; uu < UPW1; uu++) {
-                if (uu + RB_PF >= PF1 && uu + RB_PF < UPW1) load_unit_1(uu + RB_PF);
-                if (uu == 0) { // (PF1 < RB_PF: catch up)
+                if (uu + RB_PF < UPW1) load_unit_1(uu + RB_PF);
+                if (uu == 0) { // (PF0 < RB_PF: catch up)
 #pragma unroll
-                    for (int v = PF1; v < RB_PF && v < UPW1; v++) load_unit_1(v);
+                    for (int v = PF0; v < RB_PF && v < UPW1; v++) load_unit_1(v);
                 }
                 __builtin_amdgcn_sched_barrier(0);
                 if (uu < nu) {
@@ -451,12 +412,11 @@ __device__ __forceinline__ void rowblock_body(const RbPlan &m, RbParams &p) {
                     for (int tt = 0; tt < 4; tt++)
 #pragma unroll
                         for (int j = 0; j < 4; j++) acc[j] = __builtin_amdgcn_mfma_f32_4x4x1f32(av1[uu][tt], w1[uu][tt][j], acc[j], 0, 0, 0);
-                    if (!(EARLY_IMG && early_here && uu < PF0) && (!DEFER || wave < n_sum_waves)) to_image_1(uu);
+                    if (!(early_here && uu < PF0) && wave < n_sum_waves) to_image_1(uu);
                 }
-                if (STAMP && uu == 1) { asm volatile("" : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3])); GNN_RB_WSTAMP(6); } // units 0, 1 multiplied
                 __builtin_amdgcn_sched_barrier(0);
             }
-            if (SLAB_NOWAIT) store_a1();
+            store_a1();
         } else {
             if (l + 1 == Lm - 1 && wave < 4) load_tail_weights(); // (as in the branch above)
             // later layers (nets of five and more layers): the slice is loaded here, RB_MAXU units at a time
@@ -476,7 +436,6 @@ __device__ __forceinline__ void rowblock_body(const RbPlan &m, RbParams &p) {
                     if (ub + uu < nu) { unit(u0 + ub + uu, w[uu]); to_image(u0 + ub + uu, w[uu]); }
             }
         }
-        if (STAMP) { asm volatile("" : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3])); GNN_RB_STAMP(8); if (l == 1) GNN_RB_WSTAMP(7); } // MFMAs + image writes issued, results in
         if (l == 1 && y_on) *reinterpret_cast<f32x4 *>(smem + m.off_y + y_r * m.ld[Lm] + y_q * 4) = yv;
         // the two half-waves sat at different k: add them -- one row swap serves TWO values: rows r and r + 2 change halves
         // (v_permlane32_swap: the upper half of one register against the lower half of the other), after which the lower
@@ -498,15 +457,12 @@ __device__ __forceinline__ void rowblock_body(const RbPlan &m, RbParams &p) {
                 asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(x), "+v"(y));
                 half_sum[r][j] = x + y;
             }
-        if (l == 1) GNN_RB_WSTAMP(1); // this wave's MFMAs done
         if (lane_on) {
             float *part = smem + m.off_scratch + (s * 4 + 2 * hq) * N + col;
 #pragma unroll
             for (int r = 0; r < 2; r++) *reinterpret_cast<f32x4 *>(part + r * N) = half_sum[r];
         }
-        if (l == 1) GNN_RB_WSTAMP(2); // this wave at the partial-tile barrier
         __syncthreads();
-        GNN_RB_STAMP(2 * l);
         if (l + 1 == Lm - 1) break; // the layer the row tail reads: its wave sums its own row's slices (no barrier: same wave)
         // K slices summed in slice order, f applied: 4 x N/4 float4s over the threads
         const int n4 = N >> 2;
@@ -522,7 +478,6 @@ __device__ __forceinline__ void rowblock_body(const RbPlan &m, RbParams &p) {
             *reinterpret_cast<f32x4 *>(smem + m.off_act[l + 1] + er * (N + 4) + n) = v;
         }
         __syncthreads();
-        GNN_RB_STAMP(2 * l + 1);
     }
 
     // ---- row tail: one wave per batch row does the last layer, the output rule and delta_{L-2} ------------------------
@@ -544,9 +499,8 @@ __device__ __forceinline__ void rowblock_body(const RbPlan &m, RbParams &p) {
     //  test costs no miss; the NEXT batch's indices and rows are cold in L2, and index -> row behind each other did not fit under the row tail.)
     const int x_ld = x_ld_top;
     bool x_copy = false;
-    if (wave >= 4) x_copy = !(TUNE & (1 << 22)) && (p.xcopy || p.xcopyb) && p.copy_idx; // (wave-uniform)
+    if (wave >= 4) x_copy = (p.xcopy || p.xcopyb) && p.copy_idx; // (wave-uniform)
     if (wave < 4) {
-        if (TUNE & 32) __builtin_amdgcn_s_setprio(3); // the four waves on the critical path, over the image copies of the other four
         const int r = wave, row = row0 + r;
         const int K = m.kr[Lm - 1], nt = m.d[Lm], ldp = m.ld[Lm - 1];
         // (the expected row: requested first, used ~2 000 cycles from here)
@@ -570,9 +524,7 @@ __device__ __forceinline__ void rowblock_body(const RbPlan &m, RbParams &p) {
                     *reinterpret_cast<f32x4 *>(p.act[l + 1] + (size_t)row * N + n) = v;
                 }
                 *reinterpret_cast<f32x4 *>(smem + m.off_act[l + 1] + r * (N + 4) + n) = v; // (read back below by this very wave)
-                if (STAMP) asm volatile("" : "+v"(v));
             }
-            GNN_RB_STAMP(3); // this row's slices summed
         }
         const float *a = smem + m.off_act[Lm - 1] + r * (ldp + 4);
         const int kg = lane >> 2, q = lane & 3;
@@ -596,7 +548,6 @@ __device__ __forceinline__ void rowblock_body(const RbPlan &m, RbParams &p) {
         for (int i = 0; i < TK; i++)
 #pragma unroll
             for (int j = 0; j < 4; j++) z4[j] = __builtin_fmaf(av[i], tw4[i][j], z4[j]);
-        if (STAMP) { asm volatile("" : "+v"(z4)); GNN_RB_STAMP(9); } // logits: reads + FMAs
 #pragma unroll
         for (int j = 0; j < 4; j++) { // the 16 k groups: lanes q, q+4, q+8, q+12 of every row of 16, then the four rows
             float v = z4[j];
@@ -606,7 +557,6 @@ __device__ __forceinline__ void rowblock_body(const RbPlan &m, RbParams &p) {
             v = rb_sum32(v);       // LDS round trips on this chain)
             z4[j] = v;
         }
-        if (STAMP) { asm volatile("" : "+v"(z4)); GNN_RB_STAMP(10); } // k groups reduced
         // output rule on the quad: lane q holds classes 4q..4q+3
         constexpr int QX1 = 0xB1, QX2 = 0x4E; // quad_perm [1,0,3,2] / [2,3,0,1]
         f32x4 out4 = {0.f, 0.f, 0.f, 0.f}, dd4 = {0.f, 0.f, 0.f, 0.f};
@@ -686,7 +636,6 @@ __device__ __forceinline__ void rowblock_body(const RbPlan &m, RbParams &p) {
             lsum += dpp_f<QX1>(lsum);
             lsum += dpp_f<QX2>(lsum);
         }
-        if (STAMP) { asm volatile("" : "+v"(dd4)); GNN_RB_STAMP(11); } // output rule done
         float *dlast = smem + m.off_dl[Lm] + r * (16 + 4);
         if (kg == 0) {
             if (p.prob) *reinterpret_cast<f32x4 *>(p.prob + (size_t)row * 16 + 4 * q) = out4;
@@ -709,7 +658,6 @@ __device__ __forceinline__ void rowblock_body(const RbPlan &m, RbParams &p) {
             f32x4 d4[4];
 #pragma unroll
             for (int qq = 0; qq < 4; qq++) d4[qq] = *reinterpret_cast<const f32x4 *>(dlast + 4 * qq);
-            if (STAMP) { asm volatile("" : "+v"(d4[3])); GNN_RB_STAMP(5); } // delta_{L-2}'s operands read
 #pragma unroll
             for (int half = 0; half < 2; half++) {
                 const int n = lane + 64 * half;
@@ -733,10 +681,10 @@ __device__ __forceinline__ void rowblock_body(const RbPlan &m, RbParams &p) {
             }
         }
     }
-    else if (DEFER && UPW1 > 0 && Lm >= 3) {
+    else if (UPW1 > 0 && Lm >= 3) {
 #pragma unroll
         for (int uu = 0; uu < UPW1; uu++)
-            if (!(EARLY_IMG && early_here && uu < PF0) && uu < nu_1) to_image_1(uu);
+            if (!(early_here && uu < PF0) && uu < nu_1) to_image_1(uu);
     }
     if (wave >= 4 && x_copy) { // (wave-uniform) wave 4 + r: input row r of this block
         // (the row's index was fetched at the top; every load of the row in flight before the first store: as a loop of
@@ -774,11 +722,7 @@ __device__ __forceinline__ void rowblock_body(const RbPlan &m, RbParams &p) {
             }
         }
     }
-    if (TUNE & 32) __builtin_amdgcn_s_setprio(0);
-    GNN_RB_STAMP(4);  // wave 0's tail done
-    GNN_RB_WSTAMP(3); // this wave at the end of the row-tail phase
     __syncthreads();
-    GNN_RB_STAMP(12);
 
     // ---- backward data: delta_l = (delta_{l+1} . W_l^T) * f'(z_l), l = L-3 .. 1 (SCE:262-278), from the LDS images ------
     // One wave per group of 64 neurons over the WHOLE contraction: the four rows' sums stay in the accumulators and f',
@@ -832,19 +776,15 @@ __device__ __forceinline__ void rowblock_body(const RbPlan &m, RbParams &p) {
             }
         }
         if (l > 1) __syncthreads();
-        GNN_RB_STAMP(13);
     }
-    GNN_RB_WSTAMP(4); // this wave done
-    GNN_RB_STAMP(14);
 }
 
-// TUNE: development knob of tools/rowblock_probe (0 = the shipped schedule)
 // The arguments the kernel's FIRST instructions need travel ahead of the struct (RbHead: 13 dwords): the library is built with
 // -mllvm -amdgpu-kernarg-preload-count=16, so the dispatch hands them over in SGPRs and the first vector loads do not wait
 // for a scalar-cache miss on the kernel-argument segment (6.63 -> 6.45 us, tools/rowblock_probe).  The struct's own copies
 // of these fields are overwritten from them.
 #define GNN_RB_HEAD_PARAMS const float *slabs, const float *W1, const float *Wlast, const int32_t *row_idx, const float *Y, const int32_t *copy_idx, int B, int slab_rows, int ldy
-template <class SH, int ACT, int OUTK, bool STAMP = false, int TUNE = 0, bool BF = false>
+template <class SH, int ACT, int OUTK, bool BF = false>
 __global__ __launch_bounds__(RB_NT) void rowblock_kernel(GNN_RB_HEAD_PARAMS, RbParams p) {
     static_assert(!BF || SH::kL == 3 || SH::kL == 4, "the bf16 row-block kernel: nets of three and four layers");
     p.slabs = slabs; p.row_idx = row_idx; p.copy_idx = copy_idx;
@@ -859,9 +799,9 @@ __global__ __launch_bounds__(RB_NT) void rowblock_kernel(GNN_RB_HEAD_PARAMS, RbP
     if constexpr (SH::is_static) {
         constexpr RbPlan m = SH::make(); // a LOCAL constexpr object: member accesses with constant indices fold to immediates
         static_assert(m.ok, "this shape does not fit the row-block kernel");
-        rowblock_body<SH::kL, true, ACT, OUTK, STAMP, m.ns, (SH::kL >= 4 ? m.upw[1] : 0), TUNE, BF>(m, p);
+        rowblock_body<SH::kL, true, ACT, OUTK, m.ns, (SH::kL >= 4 ? m.upw[1] : 0), BF>(m, p);
     } else {
-        rowblock_body<SH::kL, false, ACT, OUTK, STAMP, MID4_MAX_SLABS, (SH::kL == 3 ? 0 : RB_MAXU), TUNE, BF>(p.plan, p);
+        rowblock_body<SH::kL, false, ACT, OUTK, MID4_MAX_SLABS, (SH::kL == 3 ? 0 : RB_MAXU), BF>(p.plan, p);
     }
 }
 

@@ -16,8 +16,8 @@ using RbMnistB = RbStaticShape<784, 100, 50, 10>;
 // middle4_kernel table: [shape policy][activation][output kind][variant]
 // variant: 0 forward only, 1 forward + backward, 2 forward + backward with A_1 from the K slabs of tile_step_kernel, 3 = 2 in bf16
 template <class SH, int OUTK> const void *mid4_fn_sh(int act, int variant) {
-#define GNN_M4(A) (variant == 3 ? reinterpret_cast<const void *>(&middle4_kernel<SH, A, OUTK, true, false, true, true>) \
-                   : variant == 2 ? reinterpret_cast<const void *>(&middle4_kernel<SH, A, OUTK, true, false, true>)  \
+#define GNN_M4(A) (variant == 3 ? reinterpret_cast<const void *>(&middle4_kernel<SH, A, OUTK, true, true, true>) \
+                   : variant == 2 ? reinterpret_cast<const void *>(&middle4_kernel<SH, A, OUTK, true, true>)  \
                    : variant == 1 ? reinterpret_cast<const void *>(&middle4_kernel<SH, A, OUTK, true>)             \
                                   : reinterpret_cast<const void *>(&middle4_kernel<SH, A, OUTK, false>))
     switch (act) {
@@ -32,11 +32,11 @@ template <class SH, int OUTK> const void *mid4_fn_sh(int act, int variant) {
 
 template <class SH, int OUTK, bool BF> const void *rb_fn_static(int act) {
     switch (act) {
-    case 0: return reinterpret_cast<const void *>(&rowblock_kernel<SH, 0, OUTK, false, 0, BF>);
-    case 1: return reinterpret_cast<const void *>(&rowblock_kernel<SH, 1, OUTK, false, 0, BF>);
-    case 2: return reinterpret_cast<const void *>(&rowblock_kernel<SH, 2, OUTK, false, 0, BF>);
-    case 3: return reinterpret_cast<const void *>(&rowblock_kernel<SH, 3, OUTK, false, 0, BF>);
-    default: return reinterpret_cast<const void *>(&rowblock_kernel<SH, 4, OUTK, false, 0, BF>);
+    case 0: return reinterpret_cast<const void *>(&rowblock_kernel<SH, 0, OUTK, BF>);
+    case 1: return reinterpret_cast<const void *>(&rowblock_kernel<SH, 1, OUTK, BF>);
+    case 2: return reinterpret_cast<const void *>(&rowblock_kernel<SH, 2, OUTK, BF>);
+    case 3: return reinterpret_cast<const void *>(&rowblock_kernel<SH, 3, OUTK, BF>);
+    default: return reinterpret_cast<const void *>(&rowblock_kernel<SH, 4, OUTK, BF>);
     }
 }
 

@@ -61,7 +61,6 @@ struct TileStepParams {
     int next_rows, next_K;       // live / padded rows of the next batch
     float *slabs;                // [n slabs][slab_rows][ldz]
     int slab_rows, ldz;
-    unsigned long long *stamps;  // STAMP builds only (tools/tile_probe.hip): 16 slots per block
     // GNN_DTYPE_BF16 (tile_step_bf16_kernel): the bf16 roundings of the operands, same shapes and leading dimensions
     const __bf16 *Ab[MAX_LAYERS]; const __bf16 *Db[MAX_LAYERS]; __bf16 *Wb[MAX_LAYERS];
     const __bf16 *Anb;
@@ -164,15 +163,14 @@ inline bool pack_tile_map(const std::vector<uint32_t> &map, uint32_t (&words)[TS
 // 16-B store that is written THROUGH the XCD's L2 (sc1): the line does not stay dirty, so the end of the kernel has nothing
 // to write back for it (a kernel boundary costs ~B / 6 TB/s for B dirty bytes, MI355X_MICROARCH.md, row `boundary`), and the
 // bytes leave while the kernel still runs.  Inline asm (the compiler has no spelling for it on a 16-B vector); the s_nop
-// covers the store-data hazard the compiler cannot see.  WT = false: a plain store.
+// covers the store-data hazard the compiler cannot see.
 // (The value must come out of an ordinary vector instruction.  Stored straight from an MFMA's destination registers the
 //  asm statement read them before the matrix pipe had written them -- the wait states between an MFMA and a memory
 //  instruction that reads its result are the compiler's to insert, and it cannot see into inline asm: the bf16 kernel's
 //  slabs came out as garbage that changed from run to run.  ts_mfma_result() supplies them.)
 __device__ __forceinline__ void ts_mfma_result(f32x4 &v) { asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 3" : "+v"(v)); }
-template <bool WT> __device__ __forceinline__ void ts_store16(float *dst, f32x4 v) {
-    if constexpr (WT) asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(dst), "v"(v) : "memory");
-    else *reinterpret_cast<f32x4 *>(dst) = v;
+__device__ __forceinline__ void ts_store16(float *dst, f32x4 v) {
+    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(dst), "v"(v) : "memory");
 }
 
 // the gradient tile's 16 B of this lane when it does not come from this launch's own product
@@ -202,22 +200,10 @@ template <int GSRC> __device__ __forceinline__ float4 ts_gradient_in(const TileS
     return g;
 }
 
-#define GNN_TS_STAMP(i)                                                                                  \
-    do {                                                                                                 \
-        if (STAMP && threadIdx.x == 0) p.stamps[blockIdx.x * 16 + (i)] = __builtin_amdgcn_s_memtime();   \
-    } while (0)
-#define GNN_TS_STAMP_REAL(i)                                                                             \
-    do {                                                                                                 \
-        if (STAMP && threadIdx.x == 0) p.stamps[blockIdx.x * 16 + (i)] = __builtin_amdgcn_s_memrealtime(); \
-    } while (0)
-
-// NW: waves per workgroup, 8 or 4 (4: half the waves to dispatch for the same tiles -- the launch ramp of ~340 workgroups is
-// a measurable share of this kernel -- at the price of two row groups per wave in the forward product)
-// WT: 1 = the slabs, 2 = the masters too are stored write-through (ts_store16)
-template <int GSRC, int GDST, bool FWD, bool STAMP = false, int NW = 8, int WT = 2>
-__global__ __launch_bounds__(NW * 64) void tile_step_kernel(TileStepParams p) {
-    constexpr int NT = NW * 64, RPW = 8 / NW; // threads; 16-row groups of a 128-row chunk per wave
-    static_assert(NW == 8 || NW == 4, "tile_step_kernel: 8 or 4 waves");
+// The slabs and the updated masters are stored write-through (ts_store16).
+template <int GSRC, int GDST, bool FWD>
+__global__ __launch_bounds__(TS_THREADS) void tile_step_kernel(TileStepParams p) {
+    constexpr int NW = TS_THREADS / 64, NT = TS_THREADS, RPW = 1; // waves; threads; 16-row groups of a 128-row chunk per wave
     constexpr int LDA = TS_TM + 16;  // gradient A image [k][m]: row stride = 16 (mod 32) floats
     constexpr int LDD = TS_TN;       // delta image [k][n]: 16 floats (lanes 16-31 land on banks 16-31)
     constexpr int LDW = TS_TN + 4;   // weight tile / partial tiles [m][n]
@@ -251,12 +237,6 @@ __global__ __launch_bounds__(NW * 64) void tile_step_kernel(TileStepParams p) {
     const bool e_ok = t < 256 && (m0 + er < L.M);
     const size_t e_off = (size_t)(m0 + er) * L.ldd + n0 + eq * 4;
 
-    GNN_TS_STAMP(0);
-    GNN_TS_STAMP_REAL(8);
-    if (STAMP && threadIdx.x == 0) { // where this workgroup runs: HW_ID (CU, SE, ..) and the XCC id
-        p.stamps[blockIdx.x * 16 + 10] = (unsigned)__builtin_amdgcn_s_getreg(0xF804);
-        p.stamps[blockIdx.x * 16 + 11] = (unsigned)__builtin_amdgcn_s_getreg(0xF814);
-    }
     // ---- everything this block reads first, all loads in flight together ------------------------
     // gradient operands of the first K chunk
     float4 va[4 * RPW], vd[RPW];
@@ -388,7 +368,6 @@ __global__ __launch_bounds__(NW * 64) void tile_step_kernel(TileStepParams p) {
             }
             __syncthreads();
             if (k0 == 0) {
-                GNN_TS_STAMP(1);
                 if (fwd) load_next(0); // lands under the gradient MFMAs and the update
             }
             if (wave < 4) {
@@ -435,7 +414,6 @@ __global__ __launch_bounds__(NW * 64) void tile_step_kernel(TileStepParams p) {
             }
         }
         const f32x4 acc = acc0 + acc1; // rows n = 4 fq + r, column m = 16 wave + fr
-        GNN_TS_STAMP(2);
         g = make_float4(acc[0], acc[1], acc[2], acc[3]);
     }
 
@@ -451,12 +429,11 @@ __global__ __launch_bounds__(NW * 64) void tile_step_kernel(TileStepParams p) {
         adj.w = sgd_adj(p.step_over_b, g.w, p.momentum, v_old.w);
         w_new = make_float4(w_old.x - adj.x, w_old.y - adj.y, w_old.z - adj.z, w_old.w - adj.w);
         if (e_ok) {
-            ts_store16<(WT >= 2)>(L.W + e_off, (f32x4){w_new.x, w_new.y, w_new.z, w_new.w});
-            ts_store16<(WT >= 2)>(L.V + e_off, (f32x4){adj.x, adj.y, adj.z, adj.w});
+            ts_store16(L.W + e_off, (f32x4){w_new.x, w_new.y, w_new.z, w_new.w});
+            ts_store16(L.V + e_off, (f32x4){adj.x, adj.y, adj.z, adj.w});
         }
     }
-    GNN_TS_STAMP(3);
-    if (!fwd) { GNN_TS_STAMP_REAL(9); return; }
+    if (!fwd) return;
 
     // ---- the next batch's first-layer sums over this tile's 64 input neurons ---------------------
     // Computed TRANSPOSED, Zp^T[n][b] = sum_m W[m][n] A'[b][m]: the accumulator then holds four
@@ -464,7 +441,6 @@ __global__ __launch_bounds__(NW * 64) void tile_step_kernel(TileStepParams p) {
     // MFMA j of chunk c: slot q holds k = 16c + 4q + j on both operands.
     if (t < 256) *reinterpret_cast<float4 *>(&sW[er * LDW + eq * 4]) = e_ok ? w_new : make_float4(0.f, 0.f, 0.f, 0.f);
     __syncthreads();
-    GNN_TS_STAMP(4);
     float *slab = p.slabs + (size_t)tm * p.slab_rows * p.ldz;
     const float *wcol = &sW[(4 * fq) * LDW + fr];
     float wv[4][4];
@@ -496,13 +472,10 @@ __global__ __launch_bounds__(NW * 64) void tile_step_kernel(TileStepParams p) {
                     }
                 }
                 const f32x4 z = z0 + z1; // rows n = 4*fq + r, column b = fr
-                GNN_TS_STAMP(5);
-                ts_store16<(WT >= 1)>(slab + (size_t)(b0 + wr + fr) * p.ldz + n0 + 4 * fq, z);
+                ts_store16(slab + (size_t)(b0 + wr + fr) * p.ldz + n0 + 4 * fq, z);
             }
         }
     }
-    GNN_TS_STAMP(6);
-    GNN_TS_STAMP_REAL(9);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -633,8 +606,8 @@ __global__ __launch_bounds__(TS_THREADS) void tile_step_bf16_kernel(TileStepPara
         adj.w = sgd_adj(p.step_over_b, g.w, p.momentum, v_old.w);
         w_new = make_float4(w_old.x - adj.x, w_old.y - adj.y, w_old.z - adj.z, w_old.w - adj.w);
         if (e_ok) {
-            ts_store16<true>(L.W + e_off, (f32x4){w_new.x, w_new.y, w_new.z, w_new.w}); // (write-through: see ts_store16)
-            ts_store16<true>(L.V + e_off, (f32x4){adj.x, adj.y, adj.z, adj.w});
+            ts_store16(L.W + e_off, (f32x4){w_new.x, w_new.y, w_new.z, w_new.w}); // (write-through: see ts_store16)
+            ts_store16(L.V + e_off, (f32x4){adj.x, adj.y, adj.z, adj.w});
             *reinterpret_cast<bf16x4 *>(p.Wb[li] + e_off) = (bf16x4){(__bf16)w_new.x, (__bf16)w_new.y, (__bf16)w_new.z, (__bf16)w_new.w};
         }
     }
@@ -663,7 +636,7 @@ __global__ __launch_bounds__(TS_THREADS) void tile_step_bf16_kernel(TileStepPara
             z = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0, join8(vn[0][0], vn[0][1]), z, 0, 0, 0);
             z = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1, join8(vn[1][0], vn[1][1]), z, 0, 0, 0);
             ts_mfma_result(z);
-            ts_store16<true>(slab + (size_t)(b0 + wave * 16 + fr) * p.ldz + n0 + 4 * fg, z); // rows n = 4fg + r, column b = fr
+            ts_store16(slab + (size_t)(b0 + wave * 16 + fr) * p.ldz + n0 + 4 * fg, z); // rows n = 4fg + r, column b = fr
         }
     }
 }

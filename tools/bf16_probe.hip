@@ -66,9 +66,9 @@ int main() {
     hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
     for (int rep = 0; rep < 3; rep++) {
         for (int v = 0; v < 2; v++) {
-            for (int i = 0; i < 50; i++) { if (v) hipLaunchKernelGGL((fwd_first_bf16<8>), dim3(f.tiling.blocks()), dim3(512), 0, s, Ab, K, Wb, N, C, N, K, f.tiling); else hipLaunchKernelGGL((fwd_first_kernel<8, false, 0>), dim3(f.tiling.blocks()), dim3(512), 0, s, f); }
+            for (int i = 0; i < 50; i++) { if (v) hipLaunchKernelGGL((fwd_first_bf16<8>), dim3(f.tiling.blocks()), dim3(512), 0, s, Ab, K, Wb, N, C, N, K, f.tiling); else hipLaunchKernelGGL((fwd_first_kernel<8, 0>), dim3(f.tiling.blocks()), dim3(512), 0, s, f); }
             CK(hipEventRecord(e0, s));
-            for (int i = 0; i < 500; i++) { if (v) hipLaunchKernelGGL((fwd_first_bf16<8>), dim3(f.tiling.blocks()), dim3(512), 0, s, Ab, K, Wb, N, C, N, K, f.tiling); else hipLaunchKernelGGL((fwd_first_kernel<8, false, 0>), dim3(f.tiling.blocks()), dim3(512), 0, s, f); }
+            for (int i = 0; i < 500; i++) { if (v) hipLaunchKernelGGL((fwd_first_bf16<8>), dim3(f.tiling.blocks()), dim3(512), 0, s, Ab, K, Wb, N, C, N, K, f.tiling); else hipLaunchKernelGGL((fwd_first_kernel<8, 0>), dim3(f.tiling.blocks()), dim3(512), 0, s, f); }
             CK(hipEventRecord(e1, s)); CK(hipEventSynchronize(e1));
             float ms; CK(hipEventElapsedTime(&ms, e0, e1));
             printf("%s: %.2f us per call\n", v ? "fwd_first, bf16-stored operands" : "fwd_first, f32 operands        ", ms * 2);

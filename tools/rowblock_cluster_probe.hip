@@ -43,8 +43,8 @@ int main(int argc, char **argv) {
     RbParams rb{}; rb.plan = make_rb_plan(dims, L); const size_t ldsr = (size_t)rb.plan.lds_floats * 4;
     for (int l = 1; l < 3; l++) { rb.W[l] = W + woff[l]; rb.act[l] = act[0][l]; }
     for (int l = 1; l < L; l++) rb.delta[l] = delta[0][l];
-    rb.Y = Y; rb.ldy = ld[3]; rb.B = B; rb.inner_act = 0; rb.slabs = slabs; rb.slab_rows = Bp; rb.stamps = stamps; rb.prob = prob[0]; rb.loss = loss[0];
-    auto k_old = rowblock_kernel<RS4, 0, 0, false>;
+    rb.Y = Y; rb.ldy = ld[3]; rb.B = B; rb.inner_act = 0; rb.slabs = slabs; rb.slab_rows = Bp; rb.prob = prob[0]; rb.loss = loss[0];
+    auto k_old = rowblock_kernel<RS4, 0, 0>;
     CK(hipFuncSetAttribute((const void *)k_old, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsr));
     RbcParams q{};
     q.W1 = W + woff[1]; q.W2 = W + woff[2]; q.act1 = act[1][1]; q.act2 = act[1][2];

@@ -1,6 +1,6 @@
 // rowblock_probe.hip -- development harness (not shipped): the training row-block kernel (rowblock_kernel.h) against
 // middle4_kernel<.., SLABS> on the 784-300-100-10 / B = 128 shapes with random slabs: outputs (tolerance: the K split of
-// the layer-2 product differs), HIP-event time per call, in-kernel phase stamps.
+// the layer-2 product differs) and HIP-event time per call of the shipped instantiations (f32 static / runtime shape, bf16).
 #include "../graph-neural-net_amd/csrc/rowblock_kernel.h"
 #include <algorithm>
 #include <cmath>
@@ -20,7 +20,7 @@ int main(int argc, char **argv) {
     int ld[4]; for (int i = 0; i < L; i++) ld[i] = pad_up(dims[i]);
     const int Bp = pad_up(B);
     size_t woff[3], np = 0; for (int l = 0; l < 3; l++) { woff[l] = np; np += (size_t)ld[l] * ld[l + 1]; }
-    float *W, *Y, *slabs; unsigned long long *stamps;
+    float *W, *Y, *slabs;
     CK(hipMalloc(&W, np * 4));
     std::vector<float> hw(np, 0.f);
     for (int l = 0; l < 3; l++) for (int i = 0; i < dims[l]; i++) for (int j = 0; j < dims[l + 1]; j++)
@@ -33,7 +33,6 @@ int main(int argc, char **argv) {
     std::vector<float> hsl((size_t)ns * Bp * ld[1], 0.f);
     for (int s = 0; s < ns; s++) for (int b = 0; b < B; b++) for (int j = 0; j < dims[1]; j++) hsl[((size_t)s * Bp + b) * ld[1] + j] = (rand() / (float)RAND_MAX - 0.45f) * 0.3f;
     CK(hipMalloc(&slabs, hsl.size() * 4)); CK(hipMemcpy(slabs, hsl.data(), hsl.size() * 4, hipMemcpyHostToDevice));
-    CK(hipMalloc(&stamps, 4096 * 16 * 8)); CK(hipMemset(stamps, 0, 4096 * 16 * 8));
     // two sets of outputs
     float *act[2][4], *delta[2][4];
     for (int v = 0; v < 2; v++) for (int l = 1; l < L; l++) {
@@ -43,16 +42,16 @@ int main(int argc, char **argv) {
     Mid4Params m4{}; m4.plan = make_mid4_plan(dims, L); const size_t lds4 = (size_t)m4.plan.lds_floats * 4;
     for (int l = 1; l < 3; l++) { m4.W[l] = W + woff[l]; m4.act[l] = act[0][l]; }
     for (int l = 1; l < L; l++) m4.delta[l] = delta[0][l];
-    m4.Y = Y; m4.ldy = ld[3]; m4.B = B; m4.inner_act = 0; m4.slabs = slabs; m4.slab_rows = Bp; m4.n_slabs = ns; m4.stamps = stamps;
+    m4.Y = Y; m4.ldy = ld[3]; m4.B = B; m4.inner_act = 0; m4.slabs = slabs; m4.slab_rows = Bp; m4.n_slabs = ns;
     RbParams rb{}; rb.plan = make_rb_plan(dims, L); const size_t ldsr = (size_t)rb.plan.lds_floats * 4;
     printf("rowblock plan ok=%d LDS %zu bytes (middle4 %zu): ksf=%d units=%d upw=%d | gb=%d ksb=%d | lw1=%d lw2=%d\n", (int)rb.plan.ok, ldsr, lds4,
            rb.plan.ksf[1], rb.plan.units[1], rb.plan.upw[1], rb.plan.gb[1], rb.plan.ksb[1], rb.plan.lw[1], rb.plan.lw[2]);
     for (int l = 1; l < 3; l++) { rb.W[l] = W + woff[l]; rb.act[l] = act[1][l]; }
     for (int l = 1; l < L; l++) rb.delta[l] = delta[1][l];
-    rb.Y = Y; rb.ldy = ld[3]; rb.B = B; rb.inner_act = 0; rb.slabs = slabs; rb.slab_rows = Bp; rb.stamps = stamps;
-    auto k_old = middle4_kernel<SS, 0, 0, true, false, true>;
-    auto k_new = rowblock_kernel<RS, 0, 0, false>;
-    auto k_new_rt = rowblock_kernel<RbRuntimeShape<4>, -1, 0, false>;
+    rb.Y = Y; rb.ldy = ld[3]; rb.B = B; rb.inner_act = 0; rb.slabs = slabs; rb.slab_rows = Bp;
+    auto k_old = middle4_kernel<SS, 0, 0, true, true>;
+    auto k_new = rowblock_kernel<RS, 0, 0>;
+    auto k_new_rt = rowblock_kernel<RbRuntimeShape<4>, -1, 0>;
     CK(hipFuncSetAttribute((const void *)k_old, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds4));
     CK(hipFuncSetAttribute((const void *)k_new, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsr));
     CK(hipFuncSetAttribute((const void *)k_new_rt, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsr));
@@ -87,74 +86,20 @@ int main(int argc, char **argv) {
         float ms; CK(hipEventElapsedTime(&ms, e0, e1));
         printf("%-44s %8.2f us per call\n", name, ms * 1000.f / n);
     };
-    auto stamps_of = [&](const char *name, auto kst, bool bf = false) {
-        CK(hipFuncSetAttribute((const void *)kst, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsr));
-        CK(hipMemsetAsync(stamps, 0, 4096 * 16 * 8, s));
-        if (bf) hipLaunchKernelGGL(kst, grid, dim3(RB_NT), ldsr, s, RBHEAD_BF(rb), rb);
-        else hipLaunchKernelGGL(kst, grid, dim3(RB_NT), ldsr, s, RBHEAD(rb), rb);
-        CK(hipStreamSynchronize(s));
-        std::vector<unsigned long long> hs((size_t)32 * 16 * 9);
-        CK(hipMemcpy(hs.data(), stamps, hs.size() * 8, hipMemcpyDeviceToHost));
-        for (int w : {0, 16}) {
-            const unsigned long long *q = &hs[w * 16];
-            printf("%s wg%-2d: slabs->A1 %llu (wave 0: loads issued +%llu, slabs in +%llu) | L2 product %llu (wave 0 done +%llu) | row tail %llu | backward %llu | total %llu cycles\n", name, w,
-                   q[1] - q[0], q[6] - q[0], q[7] - q[0], q[2] - q[1], q[8] - q[1], q[12] - q[2], q[14] - q[12], q[14] - q[0]);
-            printf("    tail of wave 0 (from the partial-tile barrier): slices summed +%llu | logits +%llu | k groups reduced +%llu | output rule +%llu | delta_{L-2} operands read +%llu | done +%llu\n",
-                   q[3] - q[2], q[9] - q[2], q[10] - q[2], q[11] - q[2], q[5] - q[2], q[4] - q[2]);
-            const char *rn[8] = {"at A1 barrier", "halves summed", "at partial barrier", "tail phase end", "done", "A operands here", "units 0,1 multiplied", "all units multiplied"};
-            for (int r : {0, 5, 6, 7, 1, 2, 3, 4}) {
-                printf("    waves %-18s (from start):", rn[r]);
-                for (int v = 0; v < 8; v++) printf(" %6lld", (long long)(hs[(size_t)(16 * 32) * (1 + r) + w * 16 + v] - q[0]));
-                printf("\n");
-            }
-        }
-    };
-#define VARIANT(T) do { \
-        auto kv = rowblock_kernel<RS, 0, 0, false, T>; \
-        CK(hipFuncSetAttribute((const void *)kv, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsr)); \
-        for (int l = 1; l < L; l++) { CK(hipMemset(act[1][l], 0xff, (size_t)Bp * ld[l] * 4)); CK(hipMemset(delta[1][l], 0xff, (size_t)Bp * ld[l] * 4)); } \
-        hipLaunchKernelGGL(kv, grid, dim3(RB_NT), ldsr, s, RBHEAD(rb), rb); \
-        compare("TUNE=" #T " vs middle4"); \
-        time_it("rowblock<static> TUNE=" #T, 500, [&]() { hipLaunchKernelGGL(kv, grid, dim3(RB_NT), ldsr, s, RBHEAD(rb), rb); }); \
-        stamps_of("TUNE=" #T, rowblock_kernel<RS, 0, 0, true, T>); \
-    } while (0)
     time_it("middle4<static, slabs> (16 waves)", 500, [&]() { hipLaunchKernelGGL(k_old, grid, dim3(1024), lds4, s, m4); });
     time_it("rowblock<runtime shape>", 500, [&]() { hipLaunchKernelGGL(k_new_rt, grid, dim3(RB_NT), ldsr, s, RBHEAD(rb), rb); });
-    VARIANT(0);   // weights first (2 units), images of waves 4-7 deferred
-    if (argc > 2) { // prefetch variants (TUNE & 7 = weight units requested before A_1 is formed, default 1; 8 = weights in front of the slabs; 0x200 / 0x600 = RB_PF 1 / 3; 128 = no early image copies)
-        if (atoi(argv[2]) == 5) goto bf16_block;
-        if (atoi(argv[2]) == 4) { VARIANT(0); VARIANT(0x1000); VARIANT(0); VARIANT(0x1002); VARIANT(0x1000); VARIANT(0); return 0; }
-        if (atoi(argv[2]) == 3) { VARIANT(0); VARIANT(0x800); VARIANT(0); VARIANT(0xa00); VARIANT(0xe00); VARIANT(0); VARIANT(0x802); return 0; }
-        if (atoi(argv[2]) == 2) { VARIANT(0); VARIANT(32); VARIANT(0); VARIANT(64); VARIANT(0); VARIANT(96); VARIANT(16); VARIANT(0); return 0; }
-        VARIANT(2); VARIANT(0); VARIANT(9); VARIANT(10); VARIANT(0); VARIANT(0x200); VARIANT(0x600); VARIANT(0); VARIANT(0x202); VARIANT(128); VARIANT(0);
-        return 0;
-    }
-    VARIANT(0x400000); // the sampled batch's row copy compiled out
-    VARIANT(0);
-    VARIANT(0x100000); // NO weight stream (constants instead of W_1's loads; wrong results): what it costs
-    VARIANT(0x200000); // ONE slab load instead of thirteen (wrong results)
-    VARIANT(0x300000); // both
-    VARIANT(0);
-    time_it("middle4<static, slabs> (16 waves)", 500, [&]() { hipLaunchKernelGGL(k_old, grid, dim3(1024), lds4, s, m4); });
-bf16_block:
-    { // the bf16 instance (BF): time and stamps only (operands: the f32 weights rounded; outputs not compared here -- tests/test_bf16_gpu.py does)
+    time_it("rowblock<static>", 500, [&]() { hipLaunchKernelGGL(k_new, grid, dim3(RB_NT), ldsr, s, RBHEAD(rb), rb); });
+    { // the bf16 instance (BF): time only (operands: the f32 weights rounded; outputs not compared here -- tests/test_bf16_gpu.py does)
         __bf16 *Wb; CK(hipMalloc(&Wb, np * 2));
         std::vector<__bf16> hb(np);
         for (size_t i = 0; i < np; i++) hb[i] = (__bf16)hw[i];
         CK(hipMemcpy(Wb, hb.data(), np * 2, hipMemcpyHostToDevice));
         for (int l = 1; l < 3; l++) { rb.Wb[l] = Wb + woff[l]; CK(hipMalloc(&rb.actb[l], (size_t)Bp * ld[l] * 2)); }
         for (int l = 1; l < L; l++) CK(hipMalloc(&rb.deltab[l], (size_t)Bp * ld[l] * 2));
-        auto kb = rowblock_kernel<RS, 0, 0, false, 0, true>;
+        auto kb = rowblock_kernel<RS, 0, 0, true>;
         CK(hipFuncSetAttribute((const void *)kb, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsr));
         time_it("rowblock<static, bf16>", 500, [&]() { hipLaunchKernelGGL(kb, grid, dim3(RB_NT), ldsr, s, RBHEAD_BF(rb), rb); });
-        stamps_of("bf16", rowblock_kernel<RS, 0, 0, true, 0, true>, true);
-#define BFVARIANT(T) do { \
-            auto kv = rowblock_kernel<RS, 0, 0, false, T, true>; \
-            CK(hipFuncSetAttribute((const void *)kv, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsr)); \
-            time_it("rowblock<static, bf16> TUNE=" #T, 500, [&]() { hipLaunchKernelGGL(kv, grid, dim3(RB_NT), ldsr, s, RBHEAD_BF(rb), rb); }); \
-        } while (0)
-        if (argc > 2) { BFVARIANT(0); BFVARIANT(2); BFVARIANT(0); BFVARIANT(9); BFVARIANT(10); BFVARIANT(0); BFVARIANT(0x1000); BFVARIANT(0x200); BFVARIANT(0x600); BFVARIANT(0); }
-        time_it("rowblock<static> TUNE=0 (f32 again)", 500, [&]() { hipLaunchKernelGGL(k_new, grid, dim3(RB_NT), ldsr, s, RBHEAD(rb), rb); });
+        time_it("rowblock<static> (f32 again)", 500, [&]() { hipLaunchKernelGGL(k_new, grid, dim3(RB_NT), ldsr, s, RBHEAD(rb), rb); });
     }
     return 0;
 }

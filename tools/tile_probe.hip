@@ -1,12 +1,9 @@
 // tile_probe.hip -- development harness (not shipped): tile_step_kernel on the 784-300-100-10 / B = 128
-// shapes with random data: HIP-event time per call of every mode and in-kernel phase stamps (STAMP build).
+// shapes with random data: HIP-event time per call of every mode, workgroup -> tile maps and sampled next batches.
 #include "../graph-neural-net_amd/csrc/tile_step_kernel.h"
-#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <vector>
-#include <map>
 using namespace gnn;
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e)); exit(1);} } while (0)
 
@@ -16,7 +13,7 @@ int main(int argc, char **argv) {
     int ld[4]; for (int i = 0; i < L; i++) ld[i] = pad_up(dims[i]);
     const int Bp = pad_up(B);
     size_t woff[3], np = 0; for (int l = 0; l < 3; l++) { woff[l] = np; np += (size_t)ld[l] * ld[l + 1]; }
-    float *W, *V, *G, *act[4], *delta[4], *slabs, *An; unsigned long long *stamps;
+    float *W, *V, *G, *act[4], *delta[4], *slabs, *An;
     CK(hipMalloc(&W, np * 4)); CK(hipMalloc(&V, np * 4)); CK(hipMalloc(&G, np * 4));
     std::vector<float> hw(np, 0.f);
     for (int l = 0; l < 3; l++) for (int i = 0; i < dims[l]; i++) for (int j = 0; j < dims[l + 1]; j++)
@@ -32,13 +29,12 @@ int main(int argc, char **argv) {
     CK(hipMalloc(&An, (size_t)Bp * ld[0] * 4)); CK(hipMemcpy(An, act[0], (size_t)Bp * ld[0] * 4, hipMemcpyDeviceToDevice));
     const int ns = (ld[0] + TS_TM - 1) / TS_TM;
     CK(hipMalloc(&slabs, (size_t)ns * Bp * ld[1] * 4));
-    CK(hipMalloc(&stamps, 4096 * 16 * 8)); CK(hipMemset(stamps, 0, 4096 * 16 * 8));
     TileStepParams t{}; t.n_layers = 3; int tiles = 0, tiles0 = 0;
     for (int l = 0; l < 3; l++) { GradLayer &gl = t.layer[l]; gl.A = act[l]; gl.lda = ld[l]; gl.D = delta[l + 1]; gl.ldd = ld[l + 1];
         gl.W = W + woff[l]; gl.V = V + woff[l]; gl.G = G + woff[l]; gl.M = ld[l]; gl.N = ld[l + 1];
         gl.tiling = make_xcd_tiling((gl.M + TS_TM - 1) / TS_TM, gl.N / TS_TN); gl.block_begin = tiles; tiles += gl.tiling.blocks(); if (!l) tiles0 = tiles; }
     t.K = Bp; t.k_true = B; t.step_over_b = 1e-4f; t.momentum = 0.9f;
-    t.An = An; t.ldan = ld[0]; t.next_rows = B; t.next_K = Bp; t.slabs = slabs; t.slab_rows = Bp; t.ldz = ld[1]; t.stamps = stamps;
+    t.An = An; t.ldan = ld[0]; t.next_rows = B; t.next_K = Bp; t.slabs = slabs; t.slab_rows = Bp; t.ldz = ld[1];
     // workgroup -> tile: the per-layer XCD rectangles of rounds 2-3 (idle blocks included), and the host-built map
     auto old_map = [&](int n_layers_used, int n_blocks) {
         std::vector<uint32_t> m((size_t)n_blocks, ~0u);
@@ -86,14 +82,8 @@ int main(int argc, char **argv) {
         time_it("tile_step<fwd only>, rectangles", 500, [&]() { hipLaunchKernelGGL((tile_step_kernel<0, 0, true>), dim3(tiles0_old), dim3(TS_THREADS), 0, s, o0); });
         time_it("tile_step<fwd only>, host-built map", 500, [&]() { hipLaunchKernelGGL((tile_step_kernel<0, 0, true>), dim3(tiles0), dim3(TS_THREADS), 0, s, n0); });
     }
-    time_it("tile_step<grad, update, fwd> slabs write-through", 500, [&]() { hipLaunchKernelGGL((tile_step_kernel<1, 2, true, false, 8, 1>), dim3(tiles), dim3(TS_THREADS), 0, s, t); });
-    time_it("tile_step<grad, update, fwd> slabs + W, V write-through", 500, [&]() { hipLaunchKernelGGL((tile_step_kernel<1, 2, true, false, 8, 2>), dim3(tiles), dim3(TS_THREADS), 0, s, t); });
-    time_it("tile_step<grad, update, fwd>", 500, [&]() { hipLaunchKernelGGL((tile_step_kernel<1, 2, true, false, 8, 0>), dim3(tiles), dim3(TS_THREADS), 0, s, t); });
-    time_it("tile_step<grad, update, fwd> slabs write-through", 500, [&]() { hipLaunchKernelGGL((tile_step_kernel<1, 2, true, false, 8, 1>), dim3(tiles), dim3(TS_THREADS), 0, s, t); });
-    time_it("tile_step<grad, update, fwd> slabs + W, V write-through", 500, [&]() { hipLaunchKernelGGL((tile_step_kernel<1, 2, true, false, 8, 2>), dim3(tiles), dim3(TS_THREADS), 0, s, t); });
     {   // a pair as in a real step: the tile kernel followed by a dependent small kernel (what the next launch waits for)
         time_it("pair: tile_step + dependent fwd-only launch", 300, [&]() { hipLaunchKernelGGL((tile_step_kernel<1, 2, true>), dim3(tiles), dim3(TS_THREADS), 0, s, t); TileStepParams u = t; u.n_layers = 1; u.tile_map = map0_new; u.map_in_args = pack_tile_map(hm0, u.map_words) ? 1 : 0; hipLaunchKernelGGL((tile_step_kernel<0, 0, true>), dim3(tiles0), dim3(TS_THREADS), 0, s, u); });
-        time_it("pair: tile_step (write-through 2) + dependent launch", 300, [&]() { hipLaunchKernelGGL((tile_step_kernel<1, 2, true, false, 8, 2>), dim3(tiles), dim3(TS_THREADS), 0, s, t); TileStepParams u = t; u.n_layers = 1; u.tile_map = map0_new; u.map_in_args = pack_tile_map(hm0, u.map_words) ? 1 : 0; hipLaunchKernelGGL((tile_step_kernel<0, 0, true>), dim3(tiles0), dim3(TS_THREADS), 0, s, u); });
     }
     {   // a SAMPLED next batch: rows gathered through an index vector from a 6 000-row data set, with and without the contiguous copy
         const int NR = 6000;
@@ -110,66 +100,9 @@ int main(int argc, char **argv) {
             time_it("next batch gathered + contiguous copy written", 500, [&]() { hipLaunchKernelGGL((tile_step_kernel<1, 2, true>), dim3(tiles), dim3(TS_THREADS), 0, s, gc); });
         }
     }
-    time_it("tile_step<grad, update, fwd> 4 waves", 500, [&]() { hipLaunchKernelGGL((tile_step_kernel<1, 2, true, false, 4>), dim3(tiles), dim3(256), 0, s, t); });
-    time_it("tile_step<grad, update, fwd> 4 waves", 500, [&]() { hipLaunchKernelGGL((tile_step_kernel<1, 2, true, false, 4>), dim3(tiles), dim3(256), 0, s, t); });
-    time_it("tile_step<grad, store G> 4 waves", 500, [&]() { hipLaunchKernelGGL((tile_step_kernel<1, 1, false, false, 4>), dim3(tiles), dim3(256), 0, s, t); });
-    time_it("tile_step<fwd only> 4 waves", 500, [&]() { TileStepParams u = t; u.n_layers = 1; u.tile_map = map0_new; u.map_in_args = pack_tile_map(hm0, u.map_words) ? 1 : 0; hipLaunchKernelGGL((tile_step_kernel<0, 0, true, false, 4>), dim3(tiles0), dim3(256), 0, s, u); });
     time_it("tile_step<grad, update>", 500, [&]() { hipLaunchKernelGGL((tile_step_kernel<1, 2, false>), dim3(tiles), dim3(TS_THREADS), 0, s, t); });
     time_it("tile_step<grad, store G>", 500, [&]() { hipLaunchKernelGGL((tile_step_kernel<1, 1, false>), dim3(tiles), dim3(TS_THREADS), 0, s, t); });
     time_it("tile_step<G, update, fwd>", 500, [&]() { hipLaunchKernelGGL((tile_step_kernel<2, 2, true>), dim3(tiles), dim3(TS_THREADS), 0, s, t); });
     time_it("tile_step<fwd only> (layer 0 tiles)", 500, [&]() { TileStepParams u = t; u.n_layers = 1; u.tile_map = map0_new; u.map_in_args = pack_tile_map(hm0, u.map_words) ? 1 : 0; hipLaunchKernelGGL((tile_step_kernel<0, 0, true>), dim3(tiles0), dim3(TS_THREADS), 0, s, u); });
-    {   // 4 waves against 8: the forward-only launch leaves W alone, so its slabs must agree bit for bit
-        std::vector<float> s8((size_t)ns * Bp * ld[1]), s4(s8.size());
-        TileStepParams u = t; u.n_layers = 1; u.tile_map = map0_new; u.map_in_args = pack_tile_map(hm0, u.map_words) ? 1 : 0;
-        hipLaunchKernelGGL((tile_step_kernel<0, 0, true>), dim3(tiles0), dim3(TS_THREADS), 0, s, u);
-        CK(hipStreamSynchronize(s)); CK(hipMemcpy(s8.data(), slabs, s8.size() * 4, hipMemcpyDeviceToHost));
-        CK(hipMemset(slabs, 0xff, s8.size() * 4));
-        hipLaunchKernelGGL((tile_step_kernel<0, 0, true, false, 4>), dim3(tiles0), dim3(256), 0, s, u);
-        CK(hipStreamSynchronize(s)); CK(hipMemcpy(s4.data(), slabs, s4.size() * 4, hipMemcpyDeviceToHost));
-        size_t bad = 0; for (size_t i = 0; i < s8.size(); i++) bad += memcmp(&s8[i], &s4[i], 4) != 0;
-        printf("forward-only slabs, 4 waves vs 8: %zu of %zu words differ\n", bad, s8.size());
-    }
-    CK(hipMemsetAsync(stamps, 0, 4096 * 16 * 8, s));
-    hipLaunchKernelGGL((tile_step_kernel<1, 2, true, true>), dim3(tiles), dim3(TS_THREADS), 0, s, t);
-    CK(hipStreamSynchronize(s));
-    std::vector<unsigned long long> hs((size_t)tiles * 16);
-    CK(hipMemcpy(hs.data(), stamps, hs.size() * 8, hipMemcpyDeviceToHost));
-    unsigned long long t0 = ~0ull, t1 = 0, s1 = 0;
-    for (int w = 0; w < tiles; w++) { if (!hs[w * 16 + 8]) continue; t0 = std::min(t0, hs[w * 16 + 8]); t1 = std::max(t1, hs[w * 16 + 9]); s1 = std::max(s1, hs[w * 16 + 8]); }
-    printf("first block start -> last block end %.2f us; last block starts %.2f us after the first\n", (t1 - t0) / 100.0, (s1 - t0) / 100.0);
-    for (int w : {0, 1, 100, 200, 246, 250, 280}) {
-        if (w >= tiles || !hs[w * 16 + 8]) continue;
-        const unsigned long long *q = &hs[w * 16];
-        printf("wg%-3d start+%.2f us: loads->LDS %llu | grad mfma %llu | reduce+update %llu | sW barrier %llu | fwd mfma %llu | store %llu | total %llu cycles (%.2f us)\n", w,
-               (q[8] - t0) / 100.0, q[1] - q[0], q[2] - q[1], q[3] - q[2], q[4] ? q[4] - q[3] : 0, q[5] ? q[5] - q[4] : 0, q[6] ? q[6] - q[5] : 0, (q[6] ? q[6] : q[3]) - q[0], (q[9] - q[8]) / 100.0);
-    }
-    // who shares a CU with whom: workgroups per (XCC, SE, CU), and the span of the members of shared CUs against the others
-    {
-        std::map<unsigned, std::vector<int>> cu;
-        for (int w = 0; w < tiles; w++) {
-            if (!hs[w * 16 + 8] || !hs[w * 16 + 9]) continue; // idle block (left before its first stamp)
-            const unsigned hw = (unsigned)hs[w * 16 + 10], xcc = (unsigned)hs[w * 16 + 11] & 15;
-            const unsigned key = (xcc << 16) | (((hw >> 13) & 7) << 8) | ((hw >> 8) & 15);
-            cu[key].push_back(w);
-        }
-        int n1 = 0, n2 = 0, n3 = 0; double d1 = 0, d2 = 0, e1 = 0, e2 = 0;
-        for (auto &kv : cu) {
-            const size_t n = kv.second.size();
-            (n == 1 ? n1 : n == 2 ? n2 : n3)++;
-            for (int w : kv.second) {
-                const double dur = (hs[w * 16 + 9] - hs[w * 16 + 8]) / 100.0, end = (hs[w * 16 + 9] - t0) / 100.0;
-                if (n == 1) { d1 = std::max(d1, dur); e1 = std::max(e1, end); } else { d2 = std::max(d2, dur); e2 = std::max(e2, end); }
-            }
-        }
-        printf("CUs with 1 / 2 / 3+ live workgroups: %d / %d / %d; longest workgroup alone on its CU %.2f us (ends +%.2f), sharing %.2f us (ends +%.2f)\n", n1, n2, n3, d1, e1, d2, e2);
-        int shown = 0;
-        for (auto &kv : cu) {
-            if (kv.second.size() < 2 || shown >= 12) continue;
-            printf("  xcc %u se %u cu %2u:", kv.first >> 16, (kv.first >> 8) & 255, kv.first & 255);
-            for (int w : kv.second) printf("  wg%-3d [+%.2f, +%.2f]", w, (hs[w * 16 + 8] - t0) / 100.0, (hs[w * 16 + 9] - t0) / 100.0);
-            printf("\n");
-            shown++;
-        }
-    }
     return 0;
 }
