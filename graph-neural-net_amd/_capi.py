@@ -78,6 +78,16 @@ SYMBOLS = [
     ("gnn_mlp_dp_set_weights", C.c_int, [_H, _dp]),
     ("gnn_mlp_dp_synchronize", C.c_int, [_H]),
     ("gnn_mlp_dp_replicas_identical", C.c_int, [_H, C.POINTER(C.c_int)]),
+    ("gnn_mlp_group_create", C.c_int, [_ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_H)]),
+    ("gnn_mlp_group_destroy", C.c_int, [_H]),
+    ("gnn_mlp_group_size", C.c_int, [_H]),
+    ("gnn_mlp_group_member", C.c_int, [_H, C.c_int, C.POINTER(_H)]),
+    ("gnn_mlp_group_upload_dataset", C.c_int, [_H, _dp, _dp, C.c_int64]),
+    ("gnn_mlp_group_upload_dataset_u8", C.c_int, [_H, _u8, _u8, C.c_int64]),
+    ("gnn_mlp_group_train_range", C.c_int, [_H, C.c_int64, C.c_int, C.c_int, _dp, _dp]),
+    ("gnn_mlp_group_train_sampled", C.c_int, [_H, _H, C.c_int, C.c_int, _dp, _dp, C.c_int]),
+    ("gnn_mlp_group_launches_per_step", C.c_int, [_H]),
+    ("gnn_mlp_group_synchronize", C.c_int, [_H]),
     ("gnn_mlp_forget_lookahead", C.c_int, [_H]),
     ("gnn_mlp_advance_time", C.c_int, [_H, C.c_int]),
     ("gnn_mlp_recover_stream", C.c_int, [_H]),

@@ -45,6 +45,27 @@ void read_env(gnn_mlp *h) {
 namespace gnn {
 namespace host {
 
+thread_local ArenaCarve *t_arena = nullptr;
+
+int dev_bytes(void **p, size_t bytes) {
+    ArenaCarve *a = t_arena;
+    if (a && !a->record) {
+        const size_t at = (a->used + 255) & ~(size_t)255;
+        if (at + bytes > a->cap) { *p = nullptr; return fail(GNN_ERR_STATE, "group arena exhausted: the members' allocations differ"); }
+        *p = a->base + at;
+        a->used = at + bytes;
+        return GNN_OK;
+    }
+    HIP_TRY(hipMalloc(p, bytes));
+    if (a) a->used = ((a->used + 255) & ~(size_t)255) + bytes;
+    return GNN_OK;
+}
+void dev_release(gnn_mlp *h, void *p) {
+    if (!p) return;
+    if (h->arena_lo && (size_t)(static_cast<char *>(p) - h->arena_lo) < h->arena_bytes) return; // (the group frees its arena)
+    (void)hipFree(p);
+}
+
 int fail(int code, const std::string &msg) {
     g_last_error = msg;
     return code;
@@ -145,8 +166,14 @@ extern "C" {
 
 const char *gnn_mlp_last_error(void) { return last_error_message(); }
 
-int gnn_mlp_create(const int32_t *dims, int n_dims, int out_kind, int inner_act, int last_act, int loss,
-                   int64_t seed, int dtype, int device, int max_batch, gnn_mlp_t **out) { return guarded([&]() -> int {
+} // extern "C"
+
+namespace gnn {
+namespace host {
+// gnn_mlp_create; shared_stream: the handle works on (and never destroys) this stream -- a member of a group (group.hip),
+// whose allocations t_arena carves out of the group's arena
+int create_handle(const int32_t *dims, int n_dims, int out_kind, int inner_act, int last_act, int loss, int64_t seed, int dtype,
+                  int device, int max_batch, hipStream_t shared_stream, gnn_mlp **out) {
     if (!out) return fail(GNN_ERR_BAD_ARG, "out is null");
     *out = nullptr;
     if (!dims || n_dims < 2) return fail(GNN_ERR_BAD_ARG, "layerDims must hold at least 2 entries (SCE:105)");
@@ -185,9 +212,14 @@ int gnn_mlp_create(const int32_t *dims, int n_dims, int out_kind, int inner_act,
     }
     h->n_pad = (int64_t)off;
 
-    auto cleanup = [&](int rc) { gnn_mlp_destroy(h); return rc; };
+    if (t_arena && !t_arena->record) { h->arena_lo = t_arena->base; h->arena_bytes = t_arena->cap; }
+    auto cleanup = [&](int rc) { destroy_handle(h); return rc; };
 #define CTRY(expr) do { int rc_ = (expr); if (rc_ != GNN_OK) return cleanup(rc_); } while (0)
-    {
+    if (shared_stream) {
+        h->own_stream = shared_stream;
+        h->shared_stream = true;
+        h->stream = h->own_stream;
+    } else {
         hipError_t e = hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking);
         if (e != hipSuccess) return cleanup(fail(GNN_ERR_HIP, std::string("hipStreamCreate: ") + hipGetErrorString(e)));
         h->stream = h->own_stream;
@@ -237,20 +269,20 @@ int gnn_mlp_create(const int32_t *dims, int n_dims, int out_kind, int inner_act,
     plan_fused(h);
     *out = h;
     return GNN_OK;
-}); }
+}
 
-int gnn_mlp_destroy(gnn_mlp_t *h) { return guarded([&]() -> int {
-    if (!h) return GNN_OK;
+void destroy_handle(gnn_mlp *h) {
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     rccl_detach_handle(h);
-    auto fr = [](void *p) { if (p) (void)hipFree(p); };
+    auto fr = [h](void *p) { dev_release(h, p); };
     fr(h->W); fr(h->V); fr(h->G_own); fr(h->act0_alt); free_eval_workspace(h);
     for (float *p : h->act) fr(p);
     for (float *p : h->delta) fr(p);
     fr(h->logits); fr(h->prob); fr(h->ybuf); fr(h->lossv); fr(h->labels); fr(h->idxbuf);
-    fr(h->stage_out); release_host_staging(h); fr(h->DX); fr(h->DY); fr(h->slabs); fr(h->ts_map); fr(h->ts_map0);
-    fr(h->Wb); fr(h->DXb);
+    fr(h->stage_out); release_host_staging(h); fr(h->slabs); fr(h->ts_map); fr(h->ts_map0);
+    if (!h->shared_dataset) { fr(h->DX); fr(h->DY); fr(h->DXb); }
+    fr(h->Wb);
     for (int i = 0; i < 2; i++) { fr(h->xstage[i]); fr(h->xstage_b[i]); }
     for (__bf16 *p : h->actb) fr(p);
     for (__bf16 *p : h->deltab) fr(p);
@@ -260,8 +292,24 @@ int gnn_mlp_destroy(gnn_mlp_t *h) { return guarded([&]() -> int {
         for (hipEvent_t e : t.start) (void)hipEventDestroy(e);
         for (hipEvent_t e : t.stop) (void)hipEventDestroy(e);
     }
-    if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
+    if (h->own_stream && !h->shared_stream) (void)hipStreamDestroy(h->own_stream);
     delete h;
+}
+
+} // namespace host
+} // namespace gnn
+
+extern "C" {
+
+int gnn_mlp_create(const int32_t *dims, int n_dims, int out_kind, int inner_act, int last_act, int loss,
+                   int64_t seed, int dtype, int device, int max_batch, gnn_mlp_t **out) { return guarded([&]() -> int {
+    return create_handle(dims, n_dims, out_kind, inner_act, last_act, loss, seed, dtype, device, max_batch, nullptr, out);
+}); }
+
+int gnn_mlp_destroy(gnn_mlp_t *h) { return guarded([&]() -> int {
+    if (!h) return GNN_OK;
+    if (h->group) return fail(GNN_ERR_STATE, "a member of a group is destroyed with its group (gnn_mlp_group_destroy)");
+    destroy_handle(h);
     return GNN_OK;
 }); }
 
@@ -372,8 +420,20 @@ static int alloc_dataset(gnn_mlp *h, int64_t N) { return guarded([&]() -> int {
     return GNN_OK;
 }); }
 
+static const char *kMemberData = "a member of a group trains on the group's dataset (gnn_mlp_group_upload_dataset)";
 int gnn_mlp_upload_dataset(gnn_mlp_t *h, const double *X, const double *Y, int64_t N) { return guarded([&]() -> int {
     TRY(check_handle(h));
+    if (h->group) return fail(GNN_ERR_STATE, kMemberData);
+    return upload_dataset_f64(h, X, Y, N);
+}); }
+int gnn_mlp_upload_dataset_u8(gnn_mlp_t *h, const uint8_t *pixels, const uint8_t *labels, int64_t N) { return guarded([&]() -> int {
+    TRY(check_handle(h));
+    if (h->group) return fail(GNN_ERR_STATE, kMemberData);
+    return upload_dataset_u8(h, pixels, labels, N);
+}); }
+} // extern "C"
+
+int gnn::host::upload_dataset_f64(gnn_mlp *h, const double *X, const double *Y, int64_t N) {
     if (!X || !Y || N <= 0) return fail(GNN_ERR_BAD_ARG, "bad dataset");
     TRY(alloc_dataset(h, N));
     const int d0 = h->dims[0], dl = h->dims[h->L - 1];
@@ -398,10 +458,9 @@ int gnn_mlp_upload_dataset(gnn_mlp_t *h, const double *X, const double *Y, int64
     TRY_LAUNCHES(h);
     h->dataset_n = N;
     return GNN_OK;
-}); }
+}
 
-int gnn_mlp_upload_dataset_u8(gnn_mlp_t *h, const uint8_t *pixels, const uint8_t *labels, int64_t N) { return guarded([&]() -> int {
-    TRY(check_handle(h));
+int gnn::host::upload_dataset_u8(gnn_mlp *h, const uint8_t *pixels, const uint8_t *labels, int64_t N) {
     if (!pixels || !labels || N <= 0) return fail(GNN_ERR_BAD_ARG, "bad dataset");
     TRY(alloc_dataset(h, N));
     const int d0 = h->dims[0], dl = h->dims[h->L - 1];
@@ -418,8 +477,9 @@ int gnn_mlp_upload_dataset_u8(gnn_mlp_t *h, const uint8_t *pixels, const uint8_t
     TRY_LAUNCHES(h);
     h->dataset_n = N;
     return GNN_OK;
-}); }
+}
 
+extern "C" {
 
 int gnn_mlp_gradient_step_range(gnn_mlp_t *h, int64_t first, int B, double step, double momentum, int noise) { return guarded([&]() -> int {
     TRY(check_handle(h));
@@ -430,13 +490,39 @@ int gnn_mlp_gradient_step_range(gnn_mlp_t *h, int64_t first, int B, double step,
 }); }
 
 
-int gnn_mlp_train_range(gnn_mlp_t *h, int64_t first, int B, int n_steps, double step, double momentum) { return guarded([&]() -> int {
-    TRY(check_handle(h));
+} // extern "C"
+
+int gnn::host::train_range_checks(gnn_mlp *h, int64_t first, int B, int n_steps, double step) {
     TRY(check_step_args(h, B, step, 0));
     if (!h->DX) return fail(GNN_ERR_STATE, "no dataset uploaded");
     if (n_steps <= 0) return fail(GNN_ERR_BAD_ARG, "n_steps must be positive (NNT:62)");
     const int64_t nb = h->dataset_n / B;
     if (nb <= 0 || first < 0 || first % B != 0) return fail(GNN_ERR_BAD_ARG, "first must be a multiple of B inside the dataset");
+    return GNN_OK;
+}
+
+// steps s .. n_steps - 1 of a train_range call, one after another
+int gnn::host::train_range_steps(gnn_mlp *h, int64_t first, int B, int s, int n_steps, double step, double momentum) {
+    const int64_t nb = h->dataset_n / B;
+    for (; s < n_steps; s++) {
+        const int64_t row0 = ((first / B + s) % nb) * B;
+        // the step's tile kernel also starts the next step -- the LAST step's too: it prepares the batch that follows the range in
+        // the data set, so that a caller who walks the data set call by call (an epoch, or a slice of one, per call) keeps the
+        // two-launch chain across calls instead of opening every call with a forward-only launch (the sums are used only if the
+        // next gradient is on exactly those rows with the weights as this step leaves them: slabs_hold)
+        hint_range(h, ((first / B + s + 1) % nb) * B, B);
+        TRY(step_on_rows(h, h->DX + (size_t)row0 * h->ld[0], h->DY + (size_t)row0 * h->ld[h->L - 1], B, step,
+                         momentum, true));
+    }
+    return GNN_OK;
+}
+
+extern "C" {
+
+int gnn_mlp_train_range(gnn_mlp_t *h, int64_t first, int B, int n_steps, double step, double momentum) { return guarded([&]() -> int {
+    TRY(check_handle(h));
+    TRY(train_range_checks(h, first, B, n_steps, step));
+    const int64_t nb = h->dataset_n / B;
     if (n_steps >= 64) try_specialize(h); // a long run repays the ~0.4 s instantiation
     int s = 0;
     // hipGraph replay (opt-in, GNN_MLP_GRAPH=1): when the request covers whole passes over the nb
@@ -507,17 +593,7 @@ int gnn_mlp_train_range(gnn_mlp_t *h, int64_t first, int B, int n_steps, double 
             s += (int)nb;
         }
     }
-    for (; s < n_steps; s++) {
-        const int64_t row0 = ((first / B + s) % nb) * B;
-        // the step's tile kernel also starts the next step -- the LAST step's too: it prepares the batch that follows the range in
-        // the data set, so that a caller who walks the data set call by call (an epoch, or a slice of one, per call) keeps the
-        // two-launch chain across calls instead of opening every call with a forward-only launch (the sums are used only if the
-        // next gradient is on exactly those rows with the weights as this step leaves them: slabs_hold)
-        hint_range(h, ((first / B + s + 1) % nb) * B, B);
-        TRY(step_on_rows(h, h->DX + (size_t)row0 * h->ld[0], h->DY + (size_t)row0 * h->ld[h->L - 1], B, step,
-                         momentum, true));
-    }
-    return GNN_OK;
+    return train_range_steps(h, first, B, s, n_steps, step, momentum);
 }); }
 
 
@@ -601,6 +677,7 @@ int gnn_mlp_bind_grad_buffer(gnn_mlp_t *h, void *dev_ptr, int64_t n_elems) { ret
 
 int gnn_mlp_set_stream(gnn_mlp_t *h, void *hip_stream) { return guarded([&]() -> int {
     TRY(check_handle(h));
+    if (h->group) return fail(GNN_ERR_STATE, "the members of a group share the group's stream");
     hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
     const bool capturing = hipStreamIsCapturing(h->stream, &st) != hipSuccess || st != hipStreamCaptureStatusNone;
     if (!capturing) HIP_TRY(hipStreamSynchronize(h->stream)); // (a capturing stream cannot be waited on)

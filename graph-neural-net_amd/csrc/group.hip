@@ -1,0 +1,262 @@
+// group.hip -- a group of nets of one shape trained side by side (include/gnn_mlp.h, gnn_mlp_group_*): hyperparameter sweeps,
+// ensembles and seed-variance runs in one call.
+//
+// The members are ordinary handles (abi.hip) whose create-time device buffers are carved out of ONE arena, member k's slice at
+// member 0's + k * S: every member makes the same allocations of the same sizes, so the pointer rule of group_kernels.h turns
+// member 0's kernel arguments into member k's.  A group step then drives MEMBER 0's control path (plan.hip: chain_gradient,
+// launch_small.hip) with GroupLaunch set, which turns each of its two launches into the grouped launch -- there is no second
+// copy of the chain logic.  What a step reads and every member shares -- the dataset, the device index ring of a sampled
+// call -- is member 0's and lies outside the arena.  Nets off the two-launch path are stepped one member after another
+// through their own handles: the same results, no speed-up.
+#include "handle.h"
+
+#include <memory>
+
+using namespace gnn;
+using namespace gnn::host;
+
+struct gnn_mlp_group {
+    int K = 0, device = 0;
+    hipStream_t stream = nullptr;
+    char *arena = nullptr;
+    size_t S = 0;                 // bytes per member (a multiple of 256)
+    std::vector<gnn_mlp *> m;
+    bool grouped = false;         // every launch of a step serves all members
+    const void *rb_fn = nullptr;  // the grouped row-block kernel (rb_group_function)
+};
+
+namespace {
+
+void free_group(gnn_mlp_group *g) {
+    if (g->stream) (void)hipStreamSynchronize(g->stream);
+    for (gnn_mlp *h : g->m) if (h) destroy_handle(h);
+    if (g->arena) (void)hipFree(g->arena);
+    if (g->stream) (void)hipStreamDestroy(g->stream);
+    delete g;
+}
+
+// the look-ahead state of a handle (handle.h: slabs / next batch / staged rows), with the pointers that name member 0's
+// buffers moved to member k's
+struct Lookahead {
+    bool slab_valid, have_next, xstage_valid;
+    const float *slab_a0, *next_a0; const int32_t *slab_idx, *next_idx;
+    int slab_B, next_B, xstage_cur;
+    bool operator==(const Lookahead &o) const {
+        return slab_valid == o.slab_valid && have_next == o.have_next && xstage_valid == o.xstage_valid && slab_a0 == o.slab_a0 &&
+               next_a0 == o.next_a0 && slab_idx == o.slab_idx && next_idx == o.next_idx && slab_B == o.slab_B &&
+               next_B == o.next_B && xstage_cur == o.xstage_cur;
+    }
+};
+template <class T> T *moved(const gnn_mlp_group *g, T *p, int k) {
+    const char *lo = g->arena;
+    if (!p || (size_t)(reinterpret_cast<const char *>(p) - lo) >= g->S) return p;
+    return reinterpret_cast<T *>(reinterpret_cast<uintptr_t>(p) + (uintptr_t)k * g->S);
+}
+Lookahead lookahead_of(const gnn_mlp_group *g, const gnn_mlp *h, int k) {
+    return Lookahead{h->slab_valid, h->have_next, h->xstage_valid, moved(g, h->slab_a0, k), moved(g, h->next_a0, k),
+                     moved(g, h->slab_idx, k), moved(g, h->next_idx, k), h->slab_B, h->next_B, h->xstage_cur};
+}
+void set_lookahead(gnn_mlp *h, const Lookahead &a) {
+    h->slab_valid = a.slab_valid; h->have_next = a.have_next; h->xstage_valid = a.xstage_valid;
+    h->slab_a0 = a.slab_a0; h->next_a0 = a.next_a0; h->slab_idx = a.slab_idx; h->next_idx = a.next_idx;
+    h->slab_B = a.slab_B; h->next_B = a.next_B; h->xstage_cur = a.xstage_cur;
+}
+
+// Before a grouped call: every member's deferred update is applied, and member 0's look-ahead state -- which the grouped
+// launches act on for everyone -- must describe every member.  If it does not (a member was stepped alone), all of it is
+// dropped: gnn_mlp_forget_lookahead keeps results bitwise, it only costs a forward-only launch.
+int enter_grouped(gnn_mlp_group *g) {
+    for (gnn_mlp *h : g->m) TRY(check_handle(h));
+    bool same = true;
+    for (int k = 1; k < g->K && same; k++) same = lookahead_of(g, g->m[0], k) == lookahead_of(g, g->m[k], 0);
+    if (!same)
+        for (gnn_mlp *h : g->m) { h->slab_valid = false; h->have_next = false; h->xstage_valid = false; h->xstage_cur = g->m[0]->xstage_cur; }
+    return GNN_OK;
+}
+// After it: member 0's step count and look-ahead state, moved to each member
+void leave_grouped(gnn_mlp_group *g, int steps_done) {
+    for (int k = 1; k < g->K; k++) {
+        g->m[k]->time += steps_done;
+        set_lookahead(g->m[k], lookahead_of(g, g->m[0], k));
+    }
+}
+
+struct GroupScope { // member 0 launches for the group while this lives
+    gnn_mlp *h;
+    GroupScope(gnn_mlp *h_, const GroupLaunch *gl) : h(h_) { h->grp = gl; }
+    ~GroupScope() { h->grp = nullptr; }
+};
+
+int group_launch(const gnn_mlp_group *g, const double *steps, const double *momenta, GroupLaunch *gl) {
+    gl->K = g->K;
+    gl->arena_lo = g->arena;
+    gl->S = g->S;
+    gl->rb_fn = g->rb_fn;
+    for (int k = 0; k < g->K; k++) { gl->step[k] = steps[k]; gl->momentum[k] = momenta[k]; }
+    return GNN_OK;
+}
+
+int check_group(gnn_mlp_group *g) {
+    if (!g) return fail(GNN_ERR_BAD_ARG, "null group");
+    HIP_TRY(hipSetDevice(g->device));
+    return GNN_OK;
+}
+int check_per_member(const gnn_mlp_group *g, const double *steps, const double *momenta) {
+    if (!steps || !momenta) return fail(GNN_ERR_BAD_ARG, "steps and momenta: one value per member, not null");
+    for (int k = 0; k < g->K; k++)
+        if (!(steps[k] > 0)) return fail(GNN_ERR_BAD_ARG, "step must be positive (SCE:301)");
+    return GNN_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int gnn_mlp_group_create(const int32_t *dims, int n_dims, int out_kind, int inner_act, int last_act, int loss,
+                         const int64_t *seeds, int n_members, int dtype, int device, int max_batch,
+                         gnn_mlp_group_t **out) { return guarded([&]() -> int {
+    if (!out) return fail(GNN_ERR_BAD_ARG, "out is null");
+    *out = nullptr;
+    if (n_members < 1 || n_members > GROUP_MAX) return fail(GNN_ERR_BAD_ARG, "a group holds 1 to 16 nets");
+    if (!seeds) return fail(GNN_ERR_BAD_ARG, "seeds is null");
+    // the record pass: one member created as gnn_mlp_create creates it (every argument checked there), its allocations counted
+    size_t S = 0;
+    {
+        ArenaCarve rec; rec.record = true;
+        gnn_mlp *probe = nullptr;
+        t_arena = &rec;
+        const int rc = create_handle(dims, n_dims, out_kind, inner_act, last_act, loss, seeds[0], dtype, device, max_batch, nullptr, &probe);
+        t_arena = nullptr;
+        if (rc != GNN_OK) return rc;
+        destroy_handle(probe);
+        S = (rec.used + 255) & ~(size_t)255;
+    }
+    std::unique_ptr<gnn_mlp_group, void (*)(gnn_mlp_group *)> g(new gnn_mlp_group(), free_group);
+    g->K = n_members; g->device = device; g->S = S;
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&g->arena), S * (size_t)n_members));
+    g->m.assign((size_t)n_members, nullptr);
+    for (int k = 0; k < n_members; k++) {
+        ArenaCarve carve; carve.base = g->arena + (size_t)k * S; carve.cap = S;
+        t_arena = &carve;
+        const int rc = create_handle(dims, n_dims, out_kind, inner_act, last_act, loss, seeds[k], dtype, device, max_batch, g->stream, &g->m[k]);
+        t_arena = nullptr;
+        if (rc != GNN_OK) return rc;
+        g->m[k]->group = g.get();
+        if ((carve.used + 255) / 256 * 256 != S) return fail(GNN_ERR_STATE, "the members' allocations differ");
+    }
+    gnn_mlp *h0 = g->m[0];
+    if (h0->chain && h0->rb) {
+        g->rb_fn = rb_group_function(h0);
+        if (g->rb_fn && hipFuncSetAttribute(g->rb_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h0->rb_lds_bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            g->rb_fn = nullptr;
+        }
+        g->grouped = g->rb_fn != nullptr;
+    }
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    *out = g.release();
+    return GNN_OK;
+}); }
+
+int gnn_mlp_group_destroy(gnn_mlp_group_t *g) { return guarded([&]() -> int {
+    if (!g) return GNN_OK;
+    (void)hipSetDevice(g->device);
+    free_group(g);
+    return GNN_OK;
+}); }
+
+int gnn_mlp_group_size(const gnn_mlp_group_t *g) { return g ? g->K : -1; }
+
+int gnn_mlp_group_member(gnn_mlp_group_t *g, int k, gnn_mlp_t **out) { return guarded([&]() -> int {
+    if (!g || !out) return fail(GNN_ERR_BAD_ARG, "null argument");
+    if (k < 0 || k >= g->K) return fail(GNN_ERR_BAD_ARG, "member index out of range");
+    *out = g->m[(size_t)k];
+    return GNN_OK;
+}); }
+
+int gnn_mlp_group_launches_per_step(const gnn_mlp_group_t *g) { return !g ? -1 : g->grouped ? 2 : 0; }
+
+int gnn_mlp_group_synchronize(gnn_mlp_group_t *g) { return guarded([&]() -> int {
+    TRY(check_group(g));
+    return gnn_mlp_synchronize(g->m[0]); // (one stream for all members)
+}); }
+
+// member 0 uploads (and owns) the data; the others borrow its buffers
+static int share_dataset(gnn_mlp_group *g) {
+    gnn_mlp *h0 = g->m[0];
+    for (int k = 1; k < g->K; k++) {
+        gnn_mlp *h = g->m[k];
+        h->DX = h0->DX; h->DY = h0->DY; h->DXb = h0->DXb; h->dataset_n = h0->dataset_n;
+        h->shared_dataset = true;
+        h->slab_valid = false; h->have_next = false; // (they name rows of the old dataset)
+    }
+    return GNN_OK;
+}
+
+int gnn_mlp_group_upload_dataset(gnn_mlp_group_t *g, const double *X, const double *Y, int64_t N) { return guarded([&]() -> int {
+    TRY(check_group(g));
+    for (gnn_mlp *h : g->m) TRY(check_handle(h));
+    TRY(upload_dataset_f64(g->m[0], X, Y, N));
+    return share_dataset(g);
+}); }
+
+int gnn_mlp_group_upload_dataset_u8(gnn_mlp_group_t *g, const uint8_t *pixels, const uint8_t *labels, int64_t N) { return guarded([&]() -> int {
+    TRY(check_group(g));
+    for (gnn_mlp *h : g->m) TRY(check_handle(h));
+    TRY(upload_dataset_u8(g->m[0], pixels, labels, N));
+    return share_dataset(g);
+}); }
+
+int gnn_mlp_group_train_range(gnn_mlp_group_t *g, int64_t first, int B, int n_steps, const double *steps,
+                              const double *momenta) { return guarded([&]() -> int {
+    TRY(check_group(g));
+    TRY(check_per_member(g, steps, momenta));
+    gnn_mlp *h0 = g->m[0];
+    TRY(train_range_checks(h0, first, B, n_steps, steps[0]));
+    if (g->K == 1 || !g->grouped) { // one member after another, each through its own handle
+        for (int k = 0; k < g->K; k++) TRY(gnn_mlp_train_range(g->m[(size_t)k], first, B, n_steps, steps[k], momenta[k]));
+        return GNN_OK;
+    }
+    TRY(enter_grouped(g));
+    GroupLaunch gl;
+    TRY(group_launch(g, steps, momenta, &gl));
+    const int t0 = h0->time;
+    int rc;
+    {
+        GroupScope scope(h0, &gl);
+        rc = train_range_steps(h0, first, B, 0, n_steps, steps[0], momenta[0]);
+    }
+    leave_grouped(g, h0->time - t0);
+    return rc;
+}); }
+
+int gnn_mlp_group_train_sampled(gnn_mlp_group_t *g, gnn_sampler_t *s, int iterations, int batch, const double *steps,
+                                const double *momenta, int noise) { return guarded([&]() -> int {
+    TRY(check_group(g));
+    TRY(check_per_member(g, steps, momenta));
+    gnn_mlp *h0 = g->m[0];
+    TRY(train_sampled_checks(h0, s, iterations, batch, steps[0], noise));
+    if (g->K == 1 || !g->grouped) { // every member draws what the sampler draws from its state at the call
+        std::unique_ptr<gnn_sampler_t, int (*)(gnn_sampler_t *)> start(sampler_copy(s), gnn_sampler_destroy);
+        for (int k = 0; k < g->K; k++) {
+            if (k) sampler_assign(s, start.get());
+            TRY(gnn_mlp_train_sampled(g->m[(size_t)k], s, iterations, batch, steps[k], momenta[k], noise));
+        }
+        return GNN_OK;
+    }
+    TRY(enter_grouped(g));
+    GroupLaunch gl;
+    TRY(group_launch(g, steps, momenta, &gl));
+    const int t0 = h0->time;
+    int rc;
+    {
+        GroupScope scope(h0, &gl);
+        rc = train_sampled_run(h0, s, iterations, batch, steps[0], momenta[0], noise);
+    }
+    leave_grouped(g, h0->time - t0);
+    return rc;
+}); }
+
+} // extern "C"

@@ -1,0 +1,87 @@
+// group_kernels.h -- the two-launch step (rowblock_kernel.h, tile_step_kernel.h) for a GROUP of nets of one shape: one launch
+// serves every member, blockIdx.y = the member.
+//
+// The pointer rule.  Every per-member device buffer a training launch touches is carved out of one arena, member k's slice
+// at member 0's + k * S (group.hip), so a grouped launch takes member 0's parameters exactly as the single-net host code
+// builds them and member k turns each pointer p into p + k * S when (p - arena_lo) < S (unsigned), and leaves it alone
+// otherwise: what all members share -- the group's data set, the device index ring of a sampled call -- lies outside the
+// arena.  Null stays null.  The arithmetic is the single-net kernels' (the same bodies), run at a different blockIdx.
+#pragma once
+#include "rowblock_kernel.h"
+#include "tile_step_kernel.h"
+
+namespace gnn {
+
+constexpr int GROUP_MAX = 16; // members of one group (include/gnn_mlp.h: gnn_mlp_group_create)
+
+struct GroupArgs {
+    const char *arena_lo;         // member 0's slice of the arena
+    unsigned long long S;         // bytes per member
+    int nbx;                      // live workgroups per member along x (the grid is padded to a multiple of 8: XCD placement)
+    float step_over_b[GROUP_MAX]; // (float)(step_k / (double)B), as step_on_rows computes it
+    float momentum[GROUP_MAX];
+};
+
+// member k's copy of a pointer of member 0 (the pointer rule above)
+template <class T> __device__ __forceinline__ T *group_rel(T *q, const GroupArgs &g, unsigned long long shift) {
+    const unsigned long long d = (unsigned long long)reinterpret_cast<const char *>(q) - (unsigned long long)g.arena_lo;
+    return d < g.S ? reinterpret_cast<T *>((unsigned long long)q + shift) : q;
+}
+
+// the tile kernel bodies (tile_step_body.inc) for member blockIdx.y: its pointers, its step and momentum
+#define TS_BID blockIdx.x
+#define TS_REL(q) group_rel((q), ga, ga_shift)
+#define TS_REL_LAYER(L) (L.A = TS_REL(L.A), L.D = TS_REL(L.D), L.W = TS_REL(L.W), L.V = TS_REL(L.V), L.G = TS_REL(L.G))
+#define TS_STEP_OVER_B ga.step_over_b[blockIdx.y]
+#define TS_MOMENTUM ga.momentum[blockIdx.y]
+template <int GSRC, int GDST, bool FWD>
+__global__ __launch_bounds__(TS_THREADS) void tile_step_group_kernel(TileStepParams p, GroupArgs ga) {
+    static_assert(GSRC <= 2, "grouped tile kernels: single-GPU forms only");
+    const unsigned long long ga_shift = (unsigned long long)blockIdx.y * ga.S;
+#include "tile_step_body.inc"
+}
+template <int GSRC, int GDST, bool FWD>
+__global__ __launch_bounds__(TS_THREADS) void tile_step_bf16_group_kernel(TileStepParams p, GroupArgs ga) {
+    static_assert(GSRC <= 2, "grouped tile kernels: single-GPU forms only");
+    const unsigned long long ga_shift = (unsigned long long)blockIdx.y * ga.S;
+#include "tile_step_bf16_body.inc"
+}
+#undef TS_BID
+#undef TS_REL
+#undef TS_REL_LAYER
+#undef TS_STEP_OVER_B
+#undef TS_MOMENTUM
+
+// rowblock_kernel for member blockIdx.y: the head arguments and every pointer of the struct follow the pointer rule
+template <class SH, int ACT, int OUTK, bool BF = false>
+__global__ __launch_bounds__(RB_NT) void rowblock_group_kernel(GNN_RB_HEAD_PARAMS, RbParams p, GroupArgs g) {
+    static_assert(!BF || SH::kL == 3 || SH::kL == 4, "the bf16 row-block kernel: nets of three and four layers");
+    if ((int)blockIdx.x >= g.nbx) return;
+    const unsigned long long sh = (unsigned long long)blockIdx.y * g.S;
+    p.slabs = group_rel(slabs, g, sh); p.row_idx = group_rel(row_idx, g, sh); p.copy_idx = group_rel(copy_idx, g, sh);
+#pragma unroll
+    for (int l = 0; l < MAX_LAYERS; l++) {
+        p.W[l] = group_rel(p.W[l], g, sh); p.act[l] = group_rel(p.act[l], g, sh); p.delta[l] = group_rel(p.delta[l], g, sh);
+        p.Wb[l] = group_rel(p.Wb[l], g, sh); p.actb[l] = group_rel(p.actb[l], g, sh); p.deltab[l] = group_rel(p.deltab[l], g, sh);
+    }
+    p.prob = group_rel(p.prob, g, sh); p.loss = group_rel(p.loss, g, sh); p.label = group_rel(p.label, g, sh);
+    p.xcopy = group_rel(p.xcopy, g, sh); p.xcopyb = group_rel(p.xcopyb, g, sh);
+    p.X = group_rel(p.X, g, sh); p.Xb = group_rel(p.Xb, g, sh);
+    if constexpr (BF) {
+        p.Wb[1] = group_rel(reinterpret_cast<const __bf16 *>(W1), g, sh);
+        if constexpr (SH::kL > 0) p.Wb[SH::kL - 2] = group_rel(reinterpret_cast<const __bf16 *>(Wlast), g, sh);
+    } else {
+        p.W[1] = group_rel(W1, g, sh);
+        if constexpr (SH::kL > 0) p.W[SH::kL - 2] = group_rel(Wlast, g, sh);
+    }
+    p.Y = group_rel(Y, g, sh); p.B = B; p.slab_rows = slab_rows; p.ldy = ldy;
+    if constexpr (SH::is_static) {
+        constexpr RbPlan m = SH::make();
+        static_assert(m.ok, "this shape does not fit the row-block kernel");
+        rowblock_body<SH::kL, true, ACT, OUTK, m.ns, (SH::kL >= 4 ? m.upw[1] : 0), BF>(m, p, blockIdx.x);
+    } else {
+        rowblock_body<SH::kL, false, ACT, OUTK, MID4_MAX_SLABS, (SH::kL == 3 ? 0 : RB_MAXU), BF>(p.plan, p, blockIdx.x);
+    }
+}
+
+} // namespace gnn

@@ -9,6 +9,7 @@
 #include "middle4_kernel.h"
 #include "rowblock_kernel.h"
 #include "tile_step_kernel.h"
+#include "group_kernels.h"
 #include "kernels.h"
 #include "eval_kernels.h"
 
@@ -26,6 +27,19 @@ struct TimerClass {
     std::vector<hipEvent_t> start, stop;
     size_t used = 0;
 };
+
+namespace gnn {
+namespace host {
+// A group call (group.hip) in progress on member 0: every launch of the two-launch step serves all K members
+// (group_kernels.h; member k's buffers at member 0's + k * S).  step / momentum per member, as the caller gave them.
+struct GroupLaunch {
+    int K = 0;
+    const char *arena_lo = nullptr; size_t S = 0;
+    const void *rb_fn = nullptr; // the grouped row-block kernel of the net (rb_group_function)
+    double step[GROUP_MAX] = {}, momentum[GROUP_MAX] = {};
+};
+} // namespace host
+} // namespace gnn
 
 struct gnn_mlp {
     int device = 0;
@@ -136,6 +150,13 @@ struct gnn_mlp {
 
     // one process per GPU with the exchange inside the library's step loop (gnn_mlp_rccl_*, dp.hip): this rank's communicator
     void *rccl_comm = nullptr; int rccl_ranks = 0, rccl_rank = 0;
+
+    // member of a group of nets (group.hip): borrowed -- gnn_mlp_destroy, the dataset uploads and gnn_mlp_set_stream refuse it
+    gnn_mlp_group *group = nullptr;
+    const gnn::host::GroupLaunch *grp = nullptr; // set on member 0 while a group call steps every member (launch_small.hip)
+    char *arena_lo = nullptr; size_t arena_bytes = 0; // this handle's slice of the group's arena: never freed by the handle
+    bool shared_dataset = false; // DX / DY / DXb are member 0's (the group's one copy)
+    bool shared_stream = false;  // own_stream is the group's
 
     hipError_t launch_error = hipSuccess; // first refused launch of a module / function-pointer kernel since the last check
     const int32_t *cur_idx = nullptr; // device row indices of the batch being stepped (fused path reads rows through them)
@@ -269,10 +290,17 @@ template <class K> void opt_in_dynamic_lds(gnn_mlp *h, K kernel, size_t bytes, b
     if (tracked) done[h->device] = true;
 }
 
+// Device allocations of gnn_mlp_create: hipMalloc, or -- while group.hip creates the members of a group -- the next
+// 256-byte-aligned slice of the member's part of the group's arena (record: hipMalloc as usual, and count the bytes).
+struct ArenaCarve { char *base = nullptr; size_t cap = 0, used = 0; bool record = false; };
+extern thread_local ArenaCarve *t_arena;
+int dev_bytes(void **p, size_t bytes);
+void dev_release(gnn_mlp *h, void *p); // hipFree, except for a slice of the handle's arena
+
 // Zero-filled device allocation.  The fill is enqueued on the HANDLE's stream: that stream is
 // non-blocking, so a legacy-stream hipMemset would not be ordered with the kernels that follow.
 template <typename T> int dev_alloc(T **p, size_t n, hipStream_t s) {
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(p), sizeof(T) * (n ? n : 1)));
+    TRY(dev_bytes(reinterpret_cast<void **>(p), sizeof(T) * (n ? n : 1)));
     HIP_TRY(hipMemsetAsync(*p, 0, sizeof(T) * (n ? n : 1), s));
     return GNN_OK;
 }
@@ -313,10 +341,18 @@ struct PeerGradients { const float *G[TS_MAX_PEERS]; int n; unsigned slice; }; /
 void plan_mid4(gnn_mlp *h);
 void plan_rowblock(gnn_mlp *h); // (after plan_chain: the kernel exists for the two-launch step only)
 void try_specialize(gnn_mlp *h);
+int static_shape_of(const gnn_mlp *h);
 void fused_forward(gnn_mlp *h, const float *a0, const float *y, int B, bool backward, bool want_prob,
                    bool want_loss, bool want_label, bool from_slabs = false, int copy_rows = RB_COPY_NONE);
 void launch_tile_step(gnn_mlp *h, int gsrc, int gdst, const NextBatch *next, const float *a0, int B, float step_over_b, float momentum,
                       bool staged = false, const PeerGradients *peers = nullptr, bool next_staged = false);
+
+// ---- group_kernels.hip / group_kernels_gnn.hip: the grouped instances ----------------------------------
+const void *rb_group_function(const gnn_mlp *h); // the grouped row-block kernel of h's net, or null (h->rb must hold)
+const void *rb_group_static_general(int which, int act, bool bf);
+// the launches of launch_small.hip for every member of h->grp: member 0's arguments, one grid row per member
+void launch_tile_step_group(gnn_mlp *h, int gsrc, int gdst, bool fwd, unsigned grid, const TileStepParams &t, int B);
+void launch_rowblock_group(gnn_mlp *h, unsigned grid, void *const *head_and_params); // (GNN_RB_HEAD_PARAMS + the RbParams)
 
 // ---- sampler.hip ---------------------------------------------------------------------------------
 // validate(validation_size) (NNT:102-113) on the device: the summed loss of dataset rows [0, n) into *d_out (fp64, device)
@@ -362,6 +398,19 @@ int step_on_host_batch_deferred(gnn_mlp *h, int B, double step, double momentum)
 void flush_pending_update(gnn_mlp *h);
 int step_on_rows(gnn_mlp *h, const float *a0, const float *y, int B, double step, double momentum, bool resident);
 int step_on_device_indices(gnn_mlp *h, const int32_t *d_idx, int B, double step, double momentum);
+
+// ---- abi.hip / sampler.hip: bodies the group entry points (group.hip) share with the single-net ones --------------------
+int create_handle(const int32_t *dims, int n_dims, int out_kind, int inner_act, int last_act, int loss, int64_t seed, int dtype,
+                  int device, int max_batch, hipStream_t shared_stream, gnn_mlp **out);
+void destroy_handle(gnn_mlp *h);
+int upload_dataset_f64(gnn_mlp *h, const double *X, const double *Y, int64_t N);
+int upload_dataset_u8(gnn_mlp *h, const uint8_t *pixels, const uint8_t *labels, int64_t N);
+int train_range_checks(gnn_mlp *h, int64_t first, int B, int n_steps, double step);
+int train_range_steps(gnn_mlp *h, int64_t first, int B, int s, int n_steps, double step, double momentum);
+int train_sampled_checks(gnn_mlp *h, gnn_sampler_t *s, int iterations, int batch, double step, int noise);
+int train_sampled_run(gnn_mlp *h, gnn_sampler_t *s, int iterations, int batch, double step, double momentum, int noise);
+gnn_sampler_t *sampler_copy(const gnn_sampler_t *s);
+void sampler_assign(gnn_sampler_t *dst, const gnn_sampler_t *src);
 
 } // namespace host
 } // namespace gnn

@@ -130,6 +130,7 @@ void plan_rowblock(gnn_mlp *h) {
 // Run-time instantiation of middle4_kernel for this net's shape (jit.h); silent no-op when the
 // net is already specialised, does not take the middle4 path, or hiprtc is unavailable.
 void try_specialize(gnn_mlp *h) {
+    if (h->grp) return; // (a group call launches the grouped instances: group_kernels.h)
     if (!h->mid4 || h->specialization != 0 || h->jit_tried) return;
     h->jit_tried = true;
     if (h->env_jit_off) return;
@@ -175,6 +176,7 @@ void fused_forward(gnn_mlp *h, const float *a0, const float *y, int B, bool back
         const float *hd_Wl = bf ? reinterpret_cast<const float *>(r.Wb[h->L - 2]) : r.W[h->L - 2];
         void *args[] = {&r.slabs, &hd_W1, &hd_Wl, &r.row_idx, &r.Y, &r.copy_idx, &r.B, &r.slab_rows, &r.ldy, &r};
         const unsigned grid = (unsigned)(pad_up(B) / 4);
+        if (h->grp) { launch_rowblock_group(h, grid, args); return; } // every member of a group (group_kernels.hip)
         TimerClass &tc = h->timers[GNN_K_MIDDLE];
         hipEvent_t ev0 = nullptr, ev1 = nullptr;
         if (h->timing && tc.used < 8192) {
@@ -260,6 +262,9 @@ void launch_tile_step(gnn_mlp *h, int gsrc, int gdst, const NextBatch *next, con
         if (staged) t.Ab[0] = h->xstage_b[h->xstage_cur];
         else if (a0) t.Ab[0] = a0_bf16(h, a0);
         if (fwd) t.Anb = next_staged ? h->xstage_b[stage_dst] : a0_bf16(h, next->a0);
+    }
+    if (h->grp) { launch_tile_step_group(h, gsrc, gdst, fwd, grid.x, t, B); return; } // every member of a group (group_kernels.hip)
+    if (h->dtype == GNN_DTYPE_BF16) {
         if (fwd_only) launch_timed(h, cls, tile_step_bf16_kernel<0, 0, true>, grid, block, 0, t);
         else if (gsrc == 1 && gdst == 1) launch_timed(h, cls, tile_step_bf16_kernel<1, 1, false>, grid, block, 0, t);
         else if (gsrc == 1 && gdst == 2 && !fwd) launch_timed(h, cls, tile_step_bf16_kernel<1, 2, false>, grid, block, 0, t);

@@ -87,23 +87,23 @@ void plan_chain(gnn_mlp *h) {
     // every allocation of the path, or none: a failure leaves the handle on the three-launch / per-layer path with nothing held
     auto give_up = [&](const char *what) {
         (void)hipGetLastError();
-        if (h->slabs) { (void)hipFree(h->slabs); h->slabs = nullptr; }
-        if (h->ts_map) { (void)hipFree(h->ts_map); h->ts_map = nullptr; }
-        if (h->ts_map0) { (void)hipFree(h->ts_map0); h->ts_map0 = nullptr; }
+        dev_release(h, h->slabs); h->slabs = nullptr;
+        dev_release(h, h->ts_map); h->ts_map = nullptr;
+        dev_release(h, h->ts_map0); h->ts_map0 = nullptr;
         for (int i = 0; i < 2; i++) {
-            if (h->xstage[i]) { (void)hipFree(h->xstage[i]); h->xstage[i] = nullptr; }
-            if (h->xstage_b[i]) { (void)hipFree(h->xstage_b[i]); h->xstage_b[i] = nullptr; }
+            dev_release(h, h->xstage[i]); h->xstage[i] = nullptr;
+            dev_release(h, h->xstage_b[i]); h->xstage_b[i] = nullptr;
         }
         h->plan_note = std::string("two-launch path not taken: ") + what;
     };
-    if (hipMalloc(reinterpret_cast<void **>(&h->slabs), sizeof(float) * n) != hipSuccess) { h->slabs = nullptr; give_up("hipMalloc of the slab buffer failed"); return; }
+    if (dev_bytes(reinterpret_cast<void **>(&h->slabs), sizeof(float) * n) != GNN_OK) { h->slabs = nullptr; give_up("hipMalloc of the slab buffer failed"); return; }
     if (hipMemsetAsync(h->slabs, 0, sizeof(float) * n, h->stream) != hipSuccess) { give_up("hipMemsetAsync of the slab buffer failed"); return; }
     for (int i = 0; i < 2; i++) {
         const size_t xn = (size_t)h->cap_rows * h->ld[0];
         if (h->dtype == GNN_DTYPE_BF16) {
-            if (hipMalloc(reinterpret_cast<void **>(&h->xstage_b[i]), sizeof(__bf16) * xn) != hipSuccess) { h->xstage_b[i] = nullptr; give_up("hipMalloc of a row staging buffer failed"); return; }
+            if (dev_bytes(reinterpret_cast<void **>(&h->xstage_b[i]), sizeof(__bf16) * xn) != GNN_OK) { h->xstage_b[i] = nullptr; give_up("hipMalloc of a row staging buffer failed"); return; }
         } else {
-            if (hipMalloc(reinterpret_cast<void **>(&h->xstage[i]), sizeof(float) * xn) != hipSuccess) { h->xstage[i] = nullptr; give_up("hipMalloc of a row staging buffer failed"); return; }
+            if (dev_bytes(reinterpret_cast<void **>(&h->xstage[i]), sizeof(float) * xn) != GNN_OK) { h->xstage[i] = nullptr; give_up("hipMalloc of a row staging buffer failed"); return; }
         }
     }
     h->n_slabs = n_slabs;
@@ -131,7 +131,7 @@ void plan_chain(gnn_mlp *h) {
         else (void)hipGetLastError();
         const std::vector<uint32_t> all = make_tile_map(ml, L - 1, cus / 8, true), first = make_tile_map(ml, 1, cus / 8, true);
         auto upload = [&](const std::vector<uint32_t> &m, uint32_t **dst) {
-            if (hipMalloc(reinterpret_cast<void **>(dst), sizeof(uint32_t) * m.size()) != hipSuccess) { *dst = nullptr; return false; }
+            if (dev_bytes(reinterpret_cast<void **>(dst), sizeof(uint32_t) * m.size()) != GNN_OK) { *dst = nullptr; return false; }
             return hipMemcpy(*dst, m.data(), sizeof(uint32_t) * m.size(), hipMemcpyHostToDevice) == hipSuccess;
         };
         if (!upload(all, &h->ts_map) || !upload(first, &h->ts_map0)) { give_up("the workgroup -> tile maps could not be placed in device memory"); return; }
@@ -296,6 +296,7 @@ void do_gradient(gnn_mlp *h, const float *a0, const float *y, int B, bool fused_
 // A handle that keeps stepping repays the ~0.4 s run-time instantiation (jit.h); never while the
 // stream is being captured into a graph (module loading is not a capturable operation).
 void maybe_specialize(gnn_mlp *h) {
+    if (h->grp) return; // (a group call launches the grouped instances: group_kernels.h)
     if (h->jit_tried || h->specialization != 0 || !h->mid4) return;
     if (++h->steps_seen < 16) return;
     hipStreamCaptureStatus st = hipStreamCaptureStatusNone;

@@ -181,13 +181,14 @@ __device__ __forceinline__ float rb_sum16(float x) {
 }
 
 // NL > 0: layer count fixed at compile time; IS_STATIC: `m` is a compile-time constant (every extent folds)
+// bid: this workgroup's row block (blockIdx.x, or the x index of a grouped launch: group_kernels.h)
 template <int NL, bool IS_STATIC, int ACT_T, int OUTK, int NSV, int UPW1, bool BF>
-__device__ __forceinline__ void rowblock_body(const RbPlan &m, RbParams &p) {
+__device__ __forceinline__ void rowblock_body(const RbPlan &m, RbParams &p, const unsigned bid) {
     const int ACT = (ACT_T >= 0) ? ACT_T : p.inner_act;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int t = threadIdx.x, lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
-    const int row0 = blockIdx.x * 4;
+    const int row0 = bid * 4;
     int x_ld_top = 0; // waves 4..7: the data-set row this wave copies during the row tail (below), a scalar load
     if (wave >= 4 && p.copy_idx && row0 + (wave - 4) < p.B)
         x_ld_top = *reinterpret_cast<const __attribute__((address_space(4))) int32_t *>(reinterpret_cast<unsigned long long>(p.copy_idx + (row0 + wave - 4)));
@@ -228,7 +229,7 @@ __device__ __forceinline__ void rowblock_body(const RbPlan &m, RbParams &p) {
     // this wave's K slice of the first register product (W_1 -> layer 2): 8-row units, 16 B per lane
     //     lane (hq, lq): rows 8u + 4hq + 0..3 of the unit, columns 128 cslice + 4 lq .. +3
     const int hq = lane >> 5, lq = lane & 31;
-    const int rot = (blockIdx.x >> 3) & 3; // the four workgroups of an XCD start their weight streams at different slices
+    const int rot = (bid >> 3) & 3; // the four workgroups of an XCD start their weight streams at different slices
     f32x4 w1[UPW1 > 0 ? UPW1 : 1][4];
     int u0_1 = 0, nu_1 = 0;
     // (uu: compile-time after unrolling.  No select on the address: a unit past the wave's slice is CLAMPED to the last
@@ -799,9 +800,9 @@ __global__ __launch_bounds__(RB_NT) void rowblock_kernel(GNN_RB_HEAD_PARAMS, RbP
     if constexpr (SH::is_static) {
         constexpr RbPlan m = SH::make(); // a LOCAL constexpr object: member accesses with constant indices fold to immediates
         static_assert(m.ok, "this shape does not fit the row-block kernel");
-        rowblock_body<SH::kL, true, ACT, OUTK, m.ns, (SH::kL >= 4 ? m.upw[1] : 0), BF>(m, p);
+        rowblock_body<SH::kL, true, ACT, OUTK, m.ns, (SH::kL >= 4 ? m.upw[1] : 0), BF>(m, p, blockIdx.x);
     } else {
-        rowblock_body<SH::kL, false, ACT, OUTK, MID4_MAX_SLABS, (SH::kL == 3 ? 0 : RB_MAXU), BF>(p.plan, p);
+        rowblock_body<SH::kL, false, ACT, OUTK, MID4_MAX_SLABS, (SH::kL == 3 ? 0 : RB_MAXU), BF>(p.plan, p, blockIdx.x);
     }
 }
 

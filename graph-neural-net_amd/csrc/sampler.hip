@@ -138,15 +138,23 @@ bool validation_losses_to_row(gnn_mlp *h, int n, float *loss_row, int *rc) {
 
 // The loop NNT:60-92 on a resident dataset; d_val != null: the observed variants (NNT:68-72, 75-79) -- after iteration i the
 // summed validation loss of rows [0, validation_size) goes to d_val[i] (device).
-static int train_sampled_impl(gnn_mlp_t *h, gnn_sampler_t *s, int iterations, int batch, double step, double momentum,
-                              int noise, int validation_size, double *d_val, float *d_rows = nullptr, int64_t row_stride = 0) {
-    TRY(check_handle(h));
+int gnn::host::train_sampled_checks(gnn_mlp *h, gnn_sampler_t *s, int iterations, int batch, double step, int noise) {
     if (!s) return fail(GNN_ERR_BAD_ARG, "null sampler");
     TRY(check_step_args(h, batch, step, noise));
     if (!h->DX) return fail(GNN_ERR_STATE, "no dataset uploaded");
     if (iterations <= 0) return fail(GNN_ERR_BAD_ARG, "iterations must be positive (NNT:62)");
     if (s->master != h->dataset_n) return fail(GNN_ERR_BAD_ARG, "sampler size differs from the dataset");
     if (batch >= s->master) return fail(GNN_ERR_BAD_ARG, "batchSize must be below the data size (NNT:63)");
+    return GNN_OK;
+}
+// the sampler's whole state: the group's fallback replays one sampler's draws for every member (group.hip)
+gnn_sampler_t *gnn::host::sampler_copy(const gnn_sampler_t *s) { return new gnn_sampler(*s); }
+void gnn::host::sampler_assign(gnn_sampler_t *dst, const gnn_sampler_t *src) { *dst = *src; }
+
+static int train_sampled_impl(gnn_mlp_t *h, gnn_sampler_t *s, int iterations, int batch, double step, double momentum,
+                              int noise, int validation_size, double *d_val, float *d_rows = nullptr, int64_t row_stride = 0) {
+    TRY(check_handle(h));
+    TRY(train_sampled_checks(h, s, iterations, batch, step, noise));
     if (iterations >= 64) try_specialize(h);
     // The exact epoch sampler is serial host work (~10 us per batch of 128: two Fenwick walks per
     // draw) of the same order as a step on the GPU, so it runs AHEAD on a worker thread, chunk by
@@ -302,6 +310,9 @@ static int train_sampled_impl(gnn_mlp_t *h, gnn_sampler_t *s, int iterations, in
     return rc;
 }
 
+int gnn::host::train_sampled_run(gnn_mlp *h, gnn_sampler_t *s, int iterations, int batch, double step, double momentum, int noise) {
+    return train_sampled_impl(h, s, iterations, batch, step, momentum, noise, 0, nullptr);
+}
 extern "C" {
 
 int gnn_mlp_train_sampled(gnn_mlp_t *h, gnn_sampler_t *s, int iterations, int batch, double step, double momentum,

@@ -1,0 +1,282 @@
+// tile_step_body.inc -- the body of tile_step_kernel (tile_step_kernel.h), included INSIDE the kernels that run it:
+// the single-net kernel and its grouped twin (group_kernels.h).  In scope: the kernel argument `p` (TileStepParams),
+// the template parameters GSRC / GDST / FWD, and five macros that say who the kernel works for:
+// TS_BID (the workgroup's index in the tile map), TS_REL(ptr) (the net's copy of a pointer of `p`), TS_REL_LAYER(L) (the same
+// for a layer descriptor), TS_STEP_OVER_B and TS_MOMENTUM.  The single-net kernels define them as the plain expressions
+// they replace (tile_step_kernel.h), the grouped twins as member k's (group_kernels.h).  Text the kernels include, not a function
+// they call, so that the single-net kernels read `p` straight from their argument segment and compile to exactly the code
+// they had before the grouped twins existed.
+    constexpr int NW = TS_THREADS / 64, NT = TS_THREADS, RPW = 1; // waves; threads; 16-row groups of a 128-row chunk per wave
+    constexpr int LDA = TS_TM + 16;  // gradient A image [k][m]: row stride = 16 (mod 32) floats
+    constexpr int LDD = TS_TN;       // delta image [k][n]: 16 floats (lanes 16-31 land on banks 16-31)
+    constexpr int LDW = TS_TN + 4;   // weight tile / partial tiles [m][n]
+    __shared__ __attribute__((aligned(16))) float sA[TS_KC * LDA];       // A chunk [128][64]
+    __shared__ __attribute__((aligned(16))) float sD[TS_KC * LDD];       // delta chunk [128][16]
+    __shared__ __attribute__((aligned(16))) float sW[TS_TM * LDW];       // the tile's (new) weights (53 KB in all)
+    const int t = threadIdx.x, lane = t & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int fr = lane & 15, fq = lane >> 4;
+
+    // by value: one batch of scalar loads, not one round trip per field as it is first used; layer 0's descriptor (nine of
+    // ten workgroups) is requested at once, beside the map entry that names the tile, not behind it
+    int li, tm, tn;
+    GradLayer L = p.layer[0];
+    if (p.map_in_args) {
+        const uint32_t w = p.map_words[TS_BID >> 1], e = (TS_BID & 1) ? w >> 16 : w & 0xffffu;
+        if (e == 0xffffu) return;
+        li = (int)(e & 7u); tm = (int)((e >> 3) & 63u); tn = (int)(e >> 9);
+    } else {
+        const uint32_t e = p.tile_map[TS_BID];
+        if (e == ~0u) return;
+        li = (int)(e & 15u); tm = (int)((e >> 4) & 0x3fffu); tn = (int)(e >> 18);
+    }
+    if (li != 0) L = p.layer[li];
+    TS_REL_LAYER(L);
+    const int m0 = tm * TS_TM, n0 = tn * TS_TN;
+    const bool fwd = FWD && li == 0; // block-uniform
+
+    // this thread's 16 B of the weight tile (waves 0..3): row er = 16*wave + fr, columns 4*fq .. 4*fq+3 -- the
+    // accumulator layout of the transposed gradient product below, so G never leaves its registers
+    const int er = (t >> 6) * 16 + fr, eq = fq;
+    const bool e_ok = t < 256 && (m0 + er < L.M);
+    const size_t e_off = (size_t)(m0 + er) * L.ldd + n0 + eq * 4;
+
+    // ---- everything this block reads first, all loads in flight together ------------------------
+    // gradient operands of the first K chunk
+    float4 va[4 * RPW], vd[RPW];
+    const int kc0 = (p.K < TS_KC) ? p.K : TS_KC;
+    // A tile wholly inside its layer, a whole first chunk, rows in place: no bounds tests, no exec-mask branches -- every wave
+    // runs this prologue before the first barrier, and a guarded 16-B load is ~13 instructions (see gemm_f32_kernel)
+    const bool interior = (m0 + TS_TM <= L.M) && (p.K >= TS_KC) && !(li == 0 && TS_REL(p.row_idx)) &&
+                          (unsigned long long)TS_KC * (unsigned)(L.lda > L.ldd ? L.lda : L.ldd) < 0xffffffffull; // 32-bit offsets
+    if (GSRC == 1 && interior) {
+#pragma unroll
+        for (int i = 0; i < 4 * RPW; i++) {
+            const int idx = t + i * NT, k = idx >> 4, q = idx & 15;
+            va[i] = *reinterpret_cast<const float4 *>(L.A + ((unsigned)k * (unsigned)L.lda + m0 + q * 4));
+        }
+#pragma unroll
+        for (int i = 0; i < RPW; i++) {
+            const int idx = t + i * NT;
+            vd[i] = *reinterpret_cast<const float4 *>(L.D + ((unsigned)(idx >> 2) * (unsigned)L.ldd + n0 + (idx & 3) * 4));
+        }
+    } else if (GSRC == 1) {
+#pragma unroll
+        for (int i = 0; i < 4 * RPW; i++) {
+            const int idx = t + i * NT, k = idx >> 4, q = idx & 15;
+            va[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (k < kc0 && m0 + q * 4 < L.M) {
+                size_t a_row = (size_t)k;
+                bool live = true;
+                if (li == 0 && TS_REL(p.row_idx)) { live = k < p.k_true; a_row = live ? (size_t)TS_REL(p.row_idx)[k] : 0; }
+                if (live) va[i] = *reinterpret_cast<const float4 *>(L.A + a_row * L.lda + m0 + q * 4);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < RPW; i++) {
+            const int idx = t + i * NT, k = idx >> 2, q = idx & 3;
+            vd[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (k < kc0) vd[i] = *reinterpret_cast<const float4 *>(L.D + (size_t)k * L.ldd + n0 + q * 4);
+        }
+    }
+    float4 w_old = make_float4(0.f, 0.f, 0.f, 0.f), v_old = w_old, g_in = w_old;
+    if (e_ok) {
+        if (GDST == 2 || FWD) w_old = *reinterpret_cast<const float4 *>(L.W + e_off);
+        if (GDST == 2) v_old = *reinterpret_cast<const float4 *>(L.V + e_off);
+    }
+    if (GSRC >= 2) g_in = ts_gradient_in<GSRC>(p, L, e_off, e_ok);
+    const bool next_plain = interior && fwd && !TS_REL(p.next_idx) && p.next_rows >= TS_KC && (unsigned long long)TS_KC * (unsigned)p.ldan < 0xffffffffull; // the first chunk of the next batch: all rows live, in place
+    const bool next_gather = (m0 + TS_TM <= L.M) && fwd && TS_REL(p.next_idx) && p.next_rows >= TS_KC;
+    const int stage_cols = (L.N / TS_TN) < 8 ? (L.N / TS_TN) : 8; // tile columns that share the staging copy's 16-row groups
+    // the next batch's rows, already in MFMA fragment form: wave -> 16 batch rows of a 128-row chunk, lane
+    // (fr, fq) -> row fr, inputs 16c + 4fq .. +3 of the tile (c = 0..3).  Straight to registers: A_0' is
+    // k-contiguous, no wave shares another's rows, and the product below needs no LDS image of it.
+    f32x4 vn[RPW][4];
+    // a sampled next batch: this lane's row index of the first chunk is fetched NOW, so that the row loads, requested
+    // ~3 000 cycles from here, do not start with a dependent round trip
+    int next_row0[RPW];
+#pragma unroll
+    for (int g = 0; g < RPW; g++) {
+        next_row0[g] = (wave + g * NW) * 16 + fr;
+        if (fwd && TS_REL(p.next_idx) && next_row0[g] < p.next_rows) next_row0[g] = TS_REL(p.next_idx)[next_row0[g]];
+    }
+    auto load_next = [&](int b0) {
+#pragma unroll
+        for (int g = 0; g < RPW; g++) {
+            const int b = b0 + (wave + g * NW) * 16 + fr;
+            if (b0 == 0 && next_plain) { // (block-uniform)
+                const float *src = TS_REL(p.An) + ((unsigned)b * (unsigned)p.ldan + m0 + 4 * fq);
+#pragma unroll
+                for (int c = 0; c < 4; c++) vn[g][c] = *reinterpret_cast<const f32x4 *>(src + c * 16);
+                continue;
+            }
+            if (b0 == 0 && next_gather) { // (block-uniform) a sampled batch, every row live, the tile inside the layer: the same
+                                          // four loads from the row the index names (fetched at the top), no bounds tests
+                const float *src = TS_REL(p.An) + ((size_t)next_row0[g] * p.ldan + m0 + 4 * fq);
+#pragma unroll
+                for (int c = 0; c < 4; c++) vn[g][c] = *reinterpret_cast<const f32x4 *>(src + c * 16);
+                continue;
+            }
+            const bool live = b < p.next_rows;
+            const size_t row = live ? (b0 == 0 ? (size_t)next_row0[g] : TS_REL(p.next_idx) ? (size_t)TS_REL(p.next_idx)[b] : (size_t)b) : 0;
+            const float *src = TS_REL(p.An) + row * p.ldan + m0 + 4 * fq;
+#pragma unroll
+            for (int c = 0; c < 4; c++) {
+                vn[g][c] = (f32x4){0.f, 0.f, 0.f, 0.f};
+                if (live && m0 + c * 16 + 4 * fq < L.M) vn[g][c] = *reinterpret_cast<const f32x4 *>(src + c * 16);
+            }
+        }
+    };
+    // (requested behind the gradient operands, below: it is needed ~2 500 cycles later, and in front of them it
+    //  delayed the first barrier by the time its 32 KB take to cross the CU's load path)
+    if (fwd && GSRC != 1) load_next(0);
+
+    // ---- gradient tile, transposed: G^T[n][m] = sum_k D[k][n] A[k][m] -----------------------------
+    // Waves 0..3 take one 16-wide m tile each over the whole K chunk; lane (fr, fq) ends with G[m = 16 wave + fr]
+    // [n = 4 fq .. 4 fq + 3]: the 16 B of W and V it loaded at the top.  No partial tiles, no second barrier.
+    // (Waves 4..7 sit on the same four SIMDs: splitting K over them bought no MFMA time and cost an LDS round trip.)
+    float4 g = g_in;
+    if (GSRC == 1) {
+        f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+        for (int k0 = 0; k0 < p.K; k0 += TS_KC) {
+            const int kc = (p.K - k0 < TS_KC) ? p.K - k0 : TS_KC; // a multiple of 16
+            if (k0) {
+                __syncthreads();
+#pragma unroll
+                for (int i = 0; i < 4 * RPW; i++) {
+                    const int idx = t + i * NT, k = idx >> 4, q = idx & 15;
+                    va[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+                    if (k < kc && m0 + q * 4 < L.M) {
+                        size_t a_row = (size_t)(k0 + k);
+                        bool live = true;
+                        if (li == 0 && TS_REL(p.row_idx)) { live = k0 + k < p.k_true; a_row = live ? (size_t)TS_REL(p.row_idx)[k0 + k] : 0; }
+                        if (live) va[i] = *reinterpret_cast<const float4 *>(L.A + a_row * L.lda + m0 + q * 4);
+                    }
+                }
+#pragma unroll
+                for (int i = 0; i < RPW; i++) {
+                    const int idx = t + i * NT, k = idx >> 2, q = idx & 3;
+                    vd[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+                    if (k < kc) vd[i] = *reinterpret_cast<const float4 *>(L.D + (size_t)(k0 + k) * L.ldd + n0 + q * 4);
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < 4 * RPW; i++) {
+                const int idx = t + i * NT, k = idx >> 4, q = idx & 15;
+                *reinterpret_cast<float4 *>(&sA[k * LDA + q * 4]) = va[i];
+            }
+#pragma unroll
+            for (int i = 0; i < RPW; i++) {
+                const int idx = t + i * NT;
+                *reinterpret_cast<float4 *>(&sD[(idx >> 2) * LDD + (idx & 3) * 4]) = vd[i];
+            }
+            __syncthreads();
+            if (k0 == 0) {
+                if (fwd) load_next(0); // lands under the gradient MFMAs and the update
+            }
+            if (wave < 4) {
+                const float *ap = &sA[fq * LDA + wave * 16 + fr];
+                const float *dp = &sD[fq * LDD + fr];
+                int kk = 0;
+                if (kc == TS_KC) {
+                    // a whole chunk (every step at B = 128): the operands of trip t + 1 are requested before the MFMAs of trip t --
+                    // trip by trip, the first MFMA of every trip waited out an LDS round trip that nothing covered (one wave per
+                    // SIMD here).  The same MFMAs on the same accumulators in the same order as the loop below.  (All 64 reads up
+                    // front took 148 registers: two workgroups no longer fit a CU, and 28 CUs hold two.)
+                    float a[2][8], d[2][8];
+#pragma unroll
+                    for (int j = 0; j < 8; j++) { a[0][j] = ap[(4 * j) * LDA]; d[0][j] = dp[(4 * j) * LDD]; }
+#pragma unroll
+                    for (int trip = 0; trip < TS_KC / 32; trip++) {
+                        const int cur = trip & 1;
+                        if (trip + 1 < TS_KC / 32) {
+#pragma unroll
+                            for (int j = 0; j < 8; j++) { a[cur ^ 1][j] = ap[(32 * (trip + 1) + 4 * j) * LDA]; d[cur ^ 1][j] = dp[(32 * (trip + 1) + 4 * j) * LDD]; }
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                        for (int j = 0; j < 8; j += 2) {
+                            acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(d[cur][j], a[cur][j], acc0, 0, 0, 0);
+                            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(d[cur][j + 1], a[cur][j + 1], acc1, 0, 0, 0);
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                    kk = TS_KC;
+                }
+                for (; kk + 32 <= kc; kk += 32) { // 8 MFMAs per trip, the trip's 16 LDS reads issued first
+                    float a[8], d[8];
+#pragma unroll
+                    for (int j = 0; j < 8; j++) { a[j] = ap[(kk + 4 * j) * LDA]; d[j] = dp[(kk + 4 * j) * LDD]; }
+#pragma unroll
+                    for (int j = 0; j < 8; j += 2) {
+                        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(d[j], a[j], acc0, 0, 0, 0);
+                        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(d[j + 1], a[j + 1], acc1, 0, 0, 0);
+                    }
+                }
+                for (; kk < kc; kk += 4)
+                    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(dp[kk * LDD], ap[kk * LDA], acc0, 0, 0, 0);
+            }
+        }
+        const f32x4 acc = acc0 + acc1; // rows n = 4 fq + r, column m = 16 wave + fr
+        g = make_float4(acc[0], acc[1], acc[2], acc[3]);
+    }
+
+    // ---- store G, or the momentum update (SCE:333-339) -------------------------------------------
+    float4 w_new = w_old;
+    if (GDST == 1) {
+        if (e_ok) *reinterpret_cast<float4 *>(L.G + e_off) = g;
+    } else if (GDST == 2) {
+        float4 adj; // ((step*G)/B) + (momentum*prev)
+        adj.x = sgd_adj(TS_STEP_OVER_B, g.x, TS_MOMENTUM, v_old.x);
+        adj.y = sgd_adj(TS_STEP_OVER_B, g.y, TS_MOMENTUM, v_old.y);
+        adj.z = sgd_adj(TS_STEP_OVER_B, g.z, TS_MOMENTUM, v_old.z);
+        adj.w = sgd_adj(TS_STEP_OVER_B, g.w, TS_MOMENTUM, v_old.w);
+        w_new = make_float4(w_old.x - adj.x, w_old.y - adj.y, w_old.z - adj.z, w_old.w - adj.w);
+        if (e_ok) {
+            ts_store16(L.W + e_off, (f32x4){w_new.x, w_new.y, w_new.z, w_new.w});
+            ts_store16(L.V + e_off, (f32x4){adj.x, adj.y, adj.z, adj.w});
+        }
+    }
+    if (!fwd) return;
+
+    // ---- the next batch's first-layer sums over this tile's 64 input neurons ---------------------
+    // Computed TRANSPOSED, Zp^T[n][b] = sum_m W[m][n] A'[b][m]: the accumulator then holds four
+    // consecutive n of one batch row per lane -- a 16-B store each, no trip through LDS.
+    // MFMA j of chunk c: slot q holds k = 16c + 4q + j on both operands.
+    if (t < 256) *reinterpret_cast<float4 *>(&sW[er * LDW + eq * 4]) = e_ok ? w_new : make_float4(0.f, 0.f, 0.f, 0.f);
+    __syncthreads();
+    float *slab = TS_REL(p.slabs) + (size_t)tm * p.slab_rows * p.ldz;
+    const float *wcol = &sW[(4 * fq) * LDW + fr];
+    float wv[4][4];
+#pragma unroll
+    for (int c = 0; c < 4; c++)
+#pragma unroll
+        for (int j = 0; j < 4; j++) wv[c][j] = wcol[(c * 16 + j) * LDW];
+    for (int b0 = 0; b0 < p.next_K; b0 += TS_KC) {
+        if (b0) load_next(b0);
+#pragma unroll
+        for (int g = 0; g < RPW; g++) {
+            const int wr = (wave + g * NW) * 16; // this wave's row group of the chunk
+            // the contiguous copy of a sampled next batch: every tile of this tile row holds the same rows; column tn copies
+            // the 16-row groups g16 with g16 % n_tn == tn (all of them in one column made its 13 workgroups the kernel's last)
+            if (TS_REL(p.stage_out) && b0 + wr < p.next_K && (((b0 + wr) >> 4) % stage_cols) == tn % stage_cols && tn < stage_cols) { // (wave-uniform; rows past the batch and columns past M are zeros in vn)
+                float *dst = TS_REL(p.stage_out) + (size_t)(b0 + wr + fr) * p.ldan + m0 + 4 * fq;
+#pragma unroll
+                for (int c = 0; c < 4; c++)
+                    if (m0 + c * 16 + 4 * fq < L.M) *reinterpret_cast<f32x4 *>(dst + c * 16) = vn[g][c];
+            }
+            if (b0 + wr < p.next_K) { // wave-uniform
+                f32x4 z0 = {0.f, 0.f, 0.f, 0.f}, z1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int c = 0; c < 4; c++) {
+#pragma unroll
+                    for (int j = 0; j < 4; j++) {
+                        if (c & 1) z1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[c][j], vn[g][c][j], z1, 0, 0, 0);
+                        else z0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[c][j], vn[g][c][j], z0, 0, 0, 0);
+                    }
+                }
+                const f32x4 z = z0 + z1; // rows n = 4*fq + r, column b = fr
+                ts_store16(slab + (size_t)(b0 + wr + fr) * p.ldz + n0 + 4 * fq, z);
+            }
+        }
+    }

@@ -376,6 +376,95 @@ class _ReplicaView(NeuralNet):
         self._h = C.c_void_p()
 
 
+class _MemberView(_ReplicaView):
+    """Member k of a NetGroup through the single-net interface (borrowed handle: closing the view does not destroy it)."""
+
+
+def _per_member(name, v, k):
+    """A scalar for every member, or one value per member."""
+    if np.ndim(v) == 0:
+        return np.full(k, float(v), dtype=np.float64)
+    a = np.ascontiguousarray(v, dtype=np.float64).ravel()
+    if a.size != k:
+        raise ValueError("%s: one value per member (%d), got %d" % (name, k, a.size))
+    return a
+
+
+class NetGroup:
+    """K = len(seeds) nets (1..16) of ONE shape trained side by side over gnn_mlp_group_* (include/gnn_mlp.h): the
+    reference's sweeps -- one MNISTTrainer run per step size / momentum / seed -- as one call.  Member k starts from
+    Random(seeds[k]) (SCE:139-156) and, after any group call, holds bit for bit what a lone net created with seeds[k]
+    holds after the same calls with steps[k], momenta[k].  `members` are borrowed single-net views (propagate,
+    count_hits_range, checkpoints, gradientStep ... work on them); the dataset belongs to the group."""
+
+    def __init__(self, layer_dims, seeds, out_kind=OUT_SOFTMAX_CE, inner_act=ACT_LEAKY_RELU, last_act=ACT_IDENTITY,
+                 loss=LOSS_HALF_SQUARED, dtype=DTYPE_F32, device=0, max_batch=1024):
+        self._lib = _capi.load()
+        self._h = C.c_void_p()
+        dims = [int(d) for d in layer_dims]
+        sd = [int(x) for x in seeds]
+        _capi.check(self._lib.gnn_mlp_group_create((C.c_int32 * len(dims))(*dims), len(dims), out_kind, _act(inner_act),
+                                                   _act(last_act), loss, (C.c_int64 * max(1, len(sd)))(*sd), len(sd),
+                                                   dtype, device, max_batch, C.byref(self._h)))
+        self.layer_dims, self.seeds, self.max_batch = dims, sd, max_batch
+        self.members = []
+        for k in range(len(sd)):
+            h = C.c_void_p()
+            _capi.check(self._lib.gnn_mlp_group_member(self._h, k, C.byref(h)))
+            self.members.append(_MemberView(self._lib, h, dims, max_batch))
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            for v in self.members:
+                v.close()
+            self._lib.gnn_mlp_group_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self):
+        return len(self.seeds)
+
+    def upload_dataset(self, X, Y):
+        X = _f64(X, self.layer_dims[0])
+        Y = _f64(Y, self.layer_dims[-1])
+        if X.shape[0] != Y.shape[0]:
+            raise ValueError("input / expected row counts differ")
+        _capi.check(self._lib.gnn_mlp_group_upload_dataset(self._h, _dp(X), _dp(Y), X.shape[0]))
+
+    def upload_dataset_u8(self, pixels, labels):
+        pixels = np.ascontiguousarray(pixels, dtype=np.uint8).reshape(-1, self.layer_dims[0])
+        labels = np.ascontiguousarray(labels, dtype=np.uint8).ravel()
+        if pixels.shape[0] != labels.size:
+            raise ValueError("pixel / label row counts differ")
+        u8 = C.POINTER(C.c_uint8)
+        _capi.check(self._lib.gnn_mlp_group_upload_dataset_u8(self._h, pixels.ctypes.data_as(u8),
+                                                              labels.ctypes.data_as(u8), labels.size))
+
+    def train_range(self, first, B, n_steps, steps, momenta):
+        """NetGroup member k: train_range(first, B, n_steps, steps[k], momenta[k]); scalars apply to every member."""
+        st, mo = _per_member("steps", steps, len(self)), _per_member("momenta", momenta, len(self))
+        _capi.check(self._lib.gnn_mlp_group_train_range(self._h, int(first), int(B), int(n_steps), _dp(st), _dp(mo)))
+
+    def train_sampled(self, sampler, iterations, batch, steps, momenta, noise=False):
+        """NNT:82-90 for every member with the draws of ONE sampler (trainer.Sampler)."""
+        st, mo = _per_member("steps", steps, len(self)), _per_member("momenta", momenta, len(self))
+        _capi.check(self._lib.gnn_mlp_group_train_sampled(self._h, sampler._h, int(iterations), int(batch), _dp(st), _dp(mo),
+                                                          int(bool(noise))))
+
+    @property
+    def launches_per_step(self):
+        """2: every launch of a group step serves all members; 0: the members are stepped one after another."""
+        return self._lib.gnn_mlp_group_launches_per_step(self._h)
+
+    def synchronize(self):
+        _capi.check(self._lib.gnn_mlp_group_synchronize(self._h))
+
+
 class DataParallelNeuralNet:
     """The NeuralNet interface over gnn_mlp_dp_* (include/gnn_mlp.h): ONE object, N device replicas,
     gradientStep sharded by rows inside the library (what a single-threaded JVM caller uses; the

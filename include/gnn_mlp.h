@@ -287,6 +287,41 @@ int gnn_mlp_dp_synchronize(gnn_mlp_dp_t *h);
 /* *identical = 1 when every replica holds the same weights, momentum and step count, bit for bit. */
 int gnn_mlp_dp_replicas_identical(gnn_mlp_dp_t *h, int *identical);
 
+/* ---- a group of nets of one shape, trained side by side ------------------------------------------
+ * The reference is run as SWEEPS: every run of MNISTTrainer is one net trained by NeuralNetTrainer with its own step size,
+ * batch size or iteration count, each with Random(1) for its weights (SCE:111) and for its sampler (NNT:42).  A group holds
+ * K = n_members in [1, 16] nets of ONE shape / kind / activations / dtype on ONE device, and ONE copy of the training data;
+ * on the two-launch path every launch of a group step serves all members (csrc/group_kernels.h).
+ * Member k after any group call is bit for bit (weights, momentum, time) the lone handle created with seeds[k] that made the
+ * same calls with steps[k], momenta[k].  Members and group calls share one stream: calls run in the order they are issued. */
+typedef struct gnn_mlp_group gnn_mlp_group_t;
+/* member k's weights are drawn as gnn_mlp_create(seed = seeds[k]) draws them (appendLayer, SCE:139-156), bit for bit */
+int gnn_mlp_group_create(const int32_t *dims, int n_dims, int out_kind, int inner_act, int last_act, int loss,
+                         const int64_t *seeds, int n_members, int dtype, int device, int max_batch,
+                         gnn_mlp_group_t **out);
+int gnn_mlp_group_destroy(gnn_mlp_group_t *g);
+int gnn_mlp_group_size(const gnn_mlp_group_t *g);
+/* Member k as an ordinary handle -- borrowed, like gnn_mlp_dp_replica: propagate, loss, argmax, count_hits_range, get/set of
+ * weights and momentum, checkpoints, gradient_step ... work on it.  gnn_mlp_destroy, gnn_mlp_upload_dataset* and
+ * gnn_mlp_set_stream on a member return GNN_ERR_STATE (the group owns its memory, dataset and stream). */
+int gnn_mlp_group_member(gnn_mlp_group_t *g, int k, gnn_mlp_t **out);
+/* ONE copy of the training data (NNT:28-43), shared by every member; the encodings of gnn_mlp_upload_dataset(_u8) */
+int gnn_mlp_group_upload_dataset(gnn_mlp_group_t *g, const double *X, const double *Y, int64_t N);
+int gnn_mlp_group_upload_dataset_u8(gnn_mlp_group_t *g, const uint8_t *pixels, const uint8_t *labels, int64_t N);
+/* gnn_mlp_train_range for every member on the SAME rows (NNT:62 loop over resident batches); member k steps with steps[k],
+ * momenta[k] (SCE:333-339) */
+int gnn_mlp_group_train_range(gnn_mlp_group_t *g, int64_t first, int B, int n_steps, const double *steps,
+                              const double *momenta);
+/* gnn_mlp_train_sampled (NNT:82-90) for every member with ONE sampler's draws -- the reference's runs all sample with
+ * Random(1), NNT:42: member k ends where a lone handle ends after train_sampled with a sampler of the same seed.  A batch
+ * shortened at a refill (NNT:149-155) is shortened for every member alike.  noise != 0 -> GNN_ERR_UNSUPPORTED (SCE:335). */
+int gnn_mlp_group_train_sampled(gnn_mlp_group_t *g, gnn_sampler_t *s, int iterations, int batch, const double *steps,
+                                const double *momenta, int noise);
+/* 2: every launch of a group step serves all members (the two-launch path); 0: the members are stepped one after another
+ * through their own handles (nets off that path, or whose row-block kernel is middle4_kernel) -- same results, no speed-up */
+int gnn_mlp_group_launches_per_step(const gnn_mlp_group_t *g);
+int gnn_mlp_group_synchronize(gnn_mlp_group_t *g);
+
 /* ---- shape specialisation ---------------------------------------------------------------------
  * The per-row-block kernel of the fused small-net path is a template over the net's shape; with
  * compile-time layer sizes it is ~1.5x faster than with sizes read from kernel arguments.
