@@ -7,6 +7,8 @@ import os
 import numpy as np
 import pytest
 
+from tests import np_oracle
+
 pytestmark = pytest.mark.gpu
 
 W_ATOL = 2e-6
@@ -54,6 +56,36 @@ def test_random_shape_against_oracle(gnn, oracle_mod, seed):
     srt = np.sort(z, axis=1)
     sure = (srt[:, -1] - srt[:, -2]) > 1e-3     # softmax is monotone: same order as the logits
     assert np.array_equal(lab[sure], ref.argmax(X)[sure]), (dims, B, inner)
+
+
+@pytest.mark.parametrize("seed", range(20))
+def test_random_shape_bf16_against_oracle(gnn, seed):
+    """The same drawn shapes with bf16 GEMM operands (per-layer bf16 GEMMs for inference and for the nets off the two-launch
+    path) against the bf16-aware fp64 oracle; tolerances as tests/test_bf16_gpu.py."""
+    dims, B, inner = random_case(seed)
+    rng = np.random.default_rng(seed)
+    X = rng.random((B, dims[0])) * (rng.random((B, dims[0])) < 0.5)
+    Y = np.eye(dims[-1])[rng.integers(0, dims[-1], B)]
+    X32 = X.astype(np.float32).astype(np.float64)     # inputs are f32 in HBM
+    net = gnn.SoftmaxCrossEntropyNeuralNet(dims, inner_act=inner, dtype=gnn.DTYPE_BF16, max_batch=B)
+    net.set_weights(net.get_weights() * 0.5)
+    w0 = net.get_weights()
+    Ws = np_oracle.split(w0, dims)
+    _, _, out = np_oracle.forward_bf16(Ws, X32, inner)
+    assert np.abs(net.propagate(X) - out).max() <= 5e-3, (dims, B, inner)
+    g = net.calculateWeightGradient(X, Y)
+    gq = np_oracle.gradient_bf16(Ws, X32, Y, inner)
+    off = 0
+    for l in range(len(dims) - 1):
+        n = dims[l] * dims[l + 1]
+        ref_l = gq[off:off + n].reshape(dims[l], dims[l + 1]); off += n
+        assert np.abs(g[l] - ref_l).max() <= 4e-3 * np.abs(ref_l).max() + 1e-7, (dims, B, inner, l)
+    w, v = w0.copy(), np.zeros_like(w0)
+    for s in range(2):
+        net.gradientStep(X, 0.0125, 0.9, False, expected=Y)
+        w, v = np_oracle.gradient_step_bf16(w, v, dims, X32, Y, 0.0125, 0.9, inner)
+    assert np.abs(net.get_weights() - w).max() <= 2e-4, (dims, B, inner)
+    assert np.abs(net.get_momentum() - v).max() <= 2e-4, (dims, B, inner)
 
 
 @pytest.mark.parametrize("seed", range(0, 20, 3))
