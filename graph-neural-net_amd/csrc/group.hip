@@ -15,20 +15,11 @@
 using namespace gnn;
 using namespace gnn::host;
 
-struct gnn_mlp_group {
-    int K = 0, device = 0;
-    hipStream_t stream = nullptr;
-    char *arena = nullptr;
-    size_t S = 0;                 // bytes per member (a multiple of 256)
-    std::vector<gnn_mlp *> m;
-    bool grouped = false;         // every launch of a step serves all members
-    const void *rb_fn = nullptr;  // the grouped row-block kernel (rb_group_function)
-};
-
 namespace {
 
 void free_group(gnn_mlp_group *g) {
     if (g->stream) (void)hipStreamSynchronize(g->stream);
+    free_group_eval(g);
     for (gnn_mlp *h : g->m) if (h) destroy_handle(h);
     if (g->arena) (void)hipFree(g->arena);
     if (g->stream) (void)hipStreamDestroy(g->stream);
@@ -155,6 +146,7 @@ int gnn_mlp_group_create(const int32_t *dims, int n_dims, int out_kind, int inne
         }
         g->grouped = g->rb_fn != nullptr;
     }
+    plan_group_eval(g.get());
     HIP_TRY(hipStreamSynchronize(g->stream));
     *out = g.release();
     return GNN_OK;

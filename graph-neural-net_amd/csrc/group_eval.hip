@@ -1,0 +1,242 @@
+// group_eval.hip -- evaluation of a group of nets (include/gnn_mlp.h: gnn_mlp_group_evaluate_range, _ensemble_range): every
+// member's accuracy and loss sum and the ensemble's mean output over rows of the group's data set, in one pass.
+//
+// Two forms, one combine kernel.  Where group_forward_kernel applies (GroupEvalPlan below) a block of rows is TWO launches:
+// the grouped forward pass (every member, blockIdx.y = k) into the group's workspace, then group_combine_kernel.  Otherwise
+// the members run one after another, each its own do_forward under its EvalScope in blocks of its own eval_block_rows, and
+// the same combine kernel reads the members' own prob / lossv / labels buffers: the same results up to near-ties, no speed-up.
+// Evaluation writes no weight, no momentum, no step count and no look-ahead state.
+#include "handle.h"
+
+#include <algorithm>
+#include <memory>
+
+using namespace gnn;
+using namespace gnn::host;
+
+namespace {
+
+// Routing (f32 nets): blocks of more rows than this take the member-after-member form even where the kernel applies -- the
+// lone per-layer GEMM chain fills the chip at thousands of rows.  Measured crossover (tools/bench_group_eval.py, MI355X, K = 4
+// and 16): at 10 000 rows the grouped pass is 1.03-1.40x the K lone calls, at 60 000 rows (blocks of 16 384) 0.75-0.88x; bf16
+// groups gain at every size.  The crossover is only bracketed -- it lies between 10 000 and 16 384 rows --
+// and the constant sits at the measured lower end: a block of 12 000 rows is routed away without a measurement of its own.
+// The two forms agree up to f32 summation order, so for f32 groups the low bits of a row's outputs depend on which side of
+// this constant the requested range falls; within one form they depend on nothing but the row.
+constexpr int kGroupedMaxBlockRowsF32 = 10000;
+
+// GroupEvalPlan: does group_forward_kernel apply to this net?  Its limits (ge_lds): 3 to 8 layers, at most 16 outputs, data
+// rows of at most 1024 padded inputs, hidden layers of at most 1024, and the two activation images + the weight / row chunks
+// within 160 KiB of LDS -- with tiles of 32 rows if that fits, else of 16.  Every net of the two-launch training path passes.
+struct GroupEvalPlan {
+    bool ok = false; int mt = 0; GroupEvalLds lds{}; const void *fn = nullptr;
+};
+GroupEvalPlan make_plan(const gnn_mlp *h) {
+    GroupEvalPlan pl;
+    const bool bf = h->dtype == GNN_DTYPE_BF16;
+    for (int mt = 2; mt >= 1 && !pl.ok; mt--) {
+        const GroupEvalLds m = ge_lds(h->ld.data(), h->L, bf, mt);
+        if (!m.ok) continue;
+        pl.ok = true; pl.mt = mt; pl.lds = m;
+        pl.fn = bf ? (mt == 2 ? reinterpret_cast<const void *>(group_forward_kernel<2, true>) : reinterpret_cast<const void *>(group_forward_kernel<1, true>))
+                   : (mt == 2 ? reinterpret_cast<const void *>(group_forward_kernel<2, false>) : reinterpret_cast<const void *>(group_forward_kernel<1, false>));
+    }
+    return pl;
+}
+
+int block_cap(const gnn_mlp *h0) { return std::max(h0->max_batch, h0->eval_rows_cap); } // (as eval_block_rows, for both dtypes)
+
+int ensure_workspace(gnn_mlp_group *g, int rows) {
+    const int want = pad_up(rows);
+    if (g->eval_ws_rows >= want) return GNN_OK;
+    HIP_TRY(hipStreamSynchronize(g->stream)); // (a smaller workspace may still be read by a queued pass)
+    if (g->eval_ws) (void)hipFree(g->eval_ws);
+    g->eval_ws = nullptr; g->eval_ws_rows = 0;
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&g->eval_ws), sizeof(float) * (size_t)g->K * want * 18));
+    g->eval_ws_rows = want;
+    return GNN_OK;
+}
+
+struct EvalOut { // device results of one call
+    unsigned long long *hits; double *sums; double *slots; // [K + 1], [K], [n_slots][GE_GROUP_MAX]
+    float *mean; int32_t *ens_label;                       // [n][d_out], [n] or null
+};
+
+// rows [first, first + n) in blocks: forward (grouped or member after member), then the combine kernel
+int run_blocks(gnn_mlp_group *g, int64_t first, int64_t n, const EvalOut &o) {
+    gnn_mlp *h0 = g->m[0];
+    const int Lm = h0->L - 1, ldo = h0->ld[Lm], d_out = h0->dims[Lm];
+    const bool bf = h0->dtype == GNN_DTYPE_BF16;
+    const int cap = block_cap(h0);
+    const bool grouped = g->eval_plan.ok && (bf || std::min<int64_t>(cap, n) <= kGroupedMaxBlockRowsF32);
+    const int block = grouped ? (int)std::min<int64_t>(cap, n) : eval_block_rows(h0, n);
+    std::vector<std::unique_ptr<EvalScope>> scopes;
+    if (grouped) {
+        TRY(ensure_workspace(g, block));
+    } else {
+        for (gnn_mlp *h : g->m) {
+            int rc = GNN_OK;
+            scopes.emplace_back(new EvalScope(h, block, &rc));
+            if (rc != GNN_OK) return rc;
+        }
+    }
+    GroupCombineParams cp{};
+    cp.K = g->K; cp.n_out = d_out; cp.ldy = ldo; cp.hits = o.hits; cp.loss_slots = o.slots;
+    int slot = 0;
+    for (int64_t off = 0; off < n; off += block) {
+        const int B = (int)std::min<int64_t>(block, n - off);
+        const float *y = h0->DY + (size_t)(first + off) * ldo;
+        if (grouped) {
+            const size_t cap_rows = (size_t)g->eval_ws_rows;
+            GroupEvalParams p{};
+            p.X = bf ? static_cast<const void *>(h0->DXb + (size_t)(first + off) * h0->ld[0])
+                     : static_cast<const void *>(h0->DX + (size_t)(first + off) * h0->ld[0]);
+            p.Y = y; p.ldy = ldo;
+            p.W = bf ? static_cast<const void *>(h0->Wb) : static_cast<const void *>(h0->W);
+            p.S = g->S;
+            p.out = g->eval_ws; p.loss = g->eval_ws + cap_rows * 16;
+            p.label = reinterpret_cast<int32_t *>(g->eval_ws + cap_rows * 17);
+            p.ws_stride = cap_rows * 18;
+            p.rows = B; p.L = h0->L;
+            for (int l = 0; l < h0->L; l++) { p.d[l] = h0->dims[l]; p.ld[l] = h0->ld[l]; }
+            for (int l = 0; l < Lm; l++) p.w_off[l] = (unsigned)h0->w_off[l];
+            p.inner_act = h0->inner_act; p.last_act = h0->last_act; p.out_kind = h0->out_kind;
+            const GroupEvalLds &m = g->eval_plan.lds;
+            p.off_img[0] = m.off_img[0]; p.off_img[1] = m.off_img[1]; p.ldi[0] = m.ldi[0]; p.ldi[1] = m.ldi[1];
+            p.off_w = m.off_w; p.off_x = m.off_x; p.off_z = m.off_z;
+            const int R = 16 * g->eval_plan.mt;
+            void *args[] = {&p};
+            HIP_TRY(hipLaunchKernel(g->eval_plan.fn, dim3((unsigned)((B + R - 1) / R), (unsigned)g->K), dim3(GE_NT), args,
+                                    (size_t)m.bytes, h0->stream));
+            for (int k = 0; k < g->K; k++) {
+                cp.out[k] = p.out + (size_t)k * p.ws_stride;
+                cp.loss[k] = p.loss + (size_t)k * p.ws_stride;
+                cp.label[k] = p.label + (size_t)k * p.ws_stride;
+            }
+            cp.ld_out = 16;
+        } else {
+            for (int k = 0; k < g->K; k++) {
+                gnn_mlp *h = g->m[(size_t)k];
+                do_forward(h, h->DX + (size_t)(first + off) * h->ld[0], y, B, true, true, true);
+                TRY_LAUNCHES(h);
+                cp.out[k] = h->prob; cp.loss[k] = h->lossv; cp.label[k] = h->labels;
+            }
+            cp.ld_out = ldo;
+        }
+        cp.rows = B; cp.Y = y; cp.slot0 = slot;
+        cp.mean_out = o.mean ? o.mean + (size_t)off * d_out : nullptr;
+        cp.ens_label = o.ens_label ? o.ens_label + off : nullptr;
+        const int nb = (B + 255) / 256;
+        hipLaunchKernelGGL(group_combine_kernel, dim3((unsigned)nb), dim3(256), 0, h0->stream, cp);
+        HIP_TRY(hipGetLastError());
+        slot += nb;
+    }
+    hipLaunchKernelGGL(group_loss_finish_kernel, dim3(1), dim3(64), 0, h0->stream, o.slots, slot, g->K, o.sums);
+    HIP_TRY(hipGetLastError());
+    return GNN_OK;
+}
+
+int n_slots_for(const gnn_mlp_group *g, int64_t n) { // an upper bound over both forms' block sizes
+    const int64_t block = std::max<int64_t>(1, std::min<int64_t>(g->m[0]->max_batch, n));
+    return (int)((n + block - 1) / block + (n + 255) / 256 + 1);
+}
+
+int check_eval_args(gnn_mlp_group *g, int64_t first, int64_t n) {
+    if (!g) return fail(GNN_ERR_BAD_ARG, "null group");
+    HIP_TRY(hipSetDevice(g->device));
+    for (gnn_mlp *h : g->m) TRY(check_handle(h)); // (a member's deferred host-batch update is applied first)
+    const gnn_mlp *h0 = g->m[0];
+    if (!h0->DX) return fail(GNN_ERR_STATE, "no dataset uploaded");
+    if (n <= 0 || first < 0 || first + n > h0->dataset_n) return fail(GNN_ERR_BAD_ARG, "rows outside the dataset");
+    return GNN_OK;
+}
+
+} // namespace
+
+namespace gnn {
+namespace host {
+
+void plan_group_eval(gnn_mlp_group *g) {
+    const GroupEvalPlan pl = make_plan(g->m[0]);
+    g->eval_plan.ok = false;
+    if (!pl.ok) return;
+    if (hipFuncSetAttribute(pl.fn, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds.bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return;
+    }
+    g->eval_plan.ok = true; g->eval_plan.mt = pl.mt; g->eval_plan.lds = pl.lds; g->eval_plan.fn = pl.fn;
+}
+
+void free_group_eval(gnn_mlp_group *g) {
+    if (g->eval_ws) (void)hipFree(g->eval_ws);
+    g->eval_ws = nullptr; g->eval_ws_rows = 0;
+}
+
+} // namespace host
+} // namespace gnn
+
+extern "C" {
+
+int gnn_mlp_group_eval_launches(const gnn_mlp_group_t *g) { return !g ? -1 : g->eval_plan.ok ? 2 : 0; }
+
+int gnn_mlp_group_evaluate_range(gnn_mlp_group_t *g, int64_t first, int64_t n, int64_t *member_hits, double *member_loss_sum,
+                                 int64_t *ensemble_hits) { return guarded([&]() -> int {
+    if (!g) return fail(GNN_ERR_BAD_ARG, "null group");
+    if (!member_hits && !member_loss_sum && !ensemble_hits) return fail(GNN_ERR_BAD_ARG, "every output is null");
+    TRY(check_eval_args(g, first, n));
+    const int K = g->K, ns = n_slots_for(g, n);
+    // [K + 1] hit counters, [K] loss sums (one readback), then the loss slots
+    const size_t head = sizeof(unsigned long long) * (size_t)(K + 1) + sizeof(double) * (size_t)K;
+    DevScratch res;
+    TRY(res.alloc(head + sizeof(double) * (size_t)ns * GE_GROUP_MAX));
+    hipStream_t st = g->m[0]->stream;
+    HIP_TRY(hipMemsetAsync(res.p, 0, head, st));
+    EvalOut o{};
+    o.hits = res.as<unsigned long long>();
+    o.sums = reinterpret_cast<double *>(o.hits + (K + 1));
+    o.slots = o.sums + K;
+    TRY(run_blocks(g, first, n, o));
+    std::vector<unsigned long long> host((size_t)(2 * K + 1));
+    static_assert(sizeof(unsigned long long) == sizeof(double), "one buffer for counters and sums");
+    HIP_TRY(hipMemcpyAsync(host.data(), res.p, head, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int k = 0; k < K; k++) {
+        if (member_hits) member_hits[k] = (int64_t)host[(size_t)k];
+        if (member_loss_sum) std::memcpy(&member_loss_sum[k], &host[(size_t)(K + 1 + k)], sizeof(double));
+    }
+    if (ensemble_hits) *ensemble_hits = (int64_t)host[(size_t)K];
+    return GNN_OK;
+}); }
+
+int gnn_mlp_group_ensemble_range(gnn_mlp_group_t *g, int64_t first, int64_t n, double *mean_out, int32_t *labels) { return guarded([&]() -> int {
+    if (!g) return fail(GNN_ERR_BAD_ARG, "null group");
+    if (!mean_out && !labels) return fail(GNN_ERR_BAD_ARG, "every output is null");
+    TRY(check_eval_args(g, first, n));
+    const gnn_mlp *h0 = g->m[0];
+    const int K = g->K, ns = n_slots_for(g, n), d_out = h0->dims[h0->L - 1];
+    const size_t head = sizeof(unsigned long long) * (size_t)(K + 1) + sizeof(double) * (size_t)K;
+    const size_t slots_b = sizeof(double) * (size_t)ns * GE_GROUP_MAX;
+    const size_t mean_b = sizeof(float) * (size_t)n * d_out, lab_b = sizeof(int32_t) * (size_t)n;
+    DevScratch res;
+    TRY(res.alloc(head + slots_b + mean_b + lab_b));
+    hipStream_t st = h0->stream;
+    HIP_TRY(hipMemsetAsync(res.p, 0, head, st));
+    EvalOut o{};
+    o.hits = res.as<unsigned long long>();
+    o.sums = reinterpret_cast<double *>(o.hits + (K + 1));
+    o.slots = o.sums + K;
+    o.mean = reinterpret_cast<float *>(res.as<char>() + head + slots_b);
+    o.ens_label = reinterpret_cast<int32_t *>(res.as<char>() + head + slots_b + mean_b);
+    TRY(run_blocks(g, first, n, o));
+    std::vector<char> host(mean_b + lab_b); // (one readback: the mean rows and the labels lie side by side)
+    HIP_TRY(hipMemcpyAsync(host.data(), o.mean, mean_b + lab_b, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (mean_out) {
+        const float *src = reinterpret_cast<const float *>(host.data());
+        for (size_t i = 0; i < (size_t)n * d_out; i++) mean_out[i] = (double)src[i];
+    }
+    if (labels) std::memcpy(labels, host.data() + mean_b, lab_b);
+    return GNN_OK;
+}); }
+
+} // extern "C"

@@ -10,6 +10,7 @@
 #include "rowblock_kernel.h"
 #include "tile_step_kernel.h"
 #include "group_kernels.h"
+#include "group_eval_kernel.h"
 #include "kernels.h"
 #include "eval_kernels.h"
 
@@ -181,8 +182,28 @@ struct gnn_mlp {
     bool env_rb_off = false;     // GNN_MLP_ROWBLOCK=0: middle4_kernel<.., SLABS> as the two-launch step's row-block kernel (round 2's form)
 };
 
+// A group of nets of one shape (group.hip; evaluation: group_eval.hip)
+struct gnn_mlp_group {
+    int K = 0, device = 0;
+    hipStream_t stream = nullptr;
+    char *arena = nullptr;
+    size_t S = 0;                 // bytes per member (a multiple of 256)
+    std::vector<gnn_mlp *> m;
+    bool grouped = false;         // every launch of a step serves all members
+    const void *rb_fn = nullptr;  // the grouped row-block kernel (rb_group_function)
+    // evaluation in grouped launches (group_eval_kernel.h): the plan made at create, and the workspace -- K x block rows x
+    // (16 + 2) words, allocated on first use, grown on demand
+    struct EvalPlan { bool ok = false; int mt = 0; gnn::GroupEvalLds lds{}; const void *fn = nullptr; } eval_plan;
+    float *eval_ws = nullptr;
+    int eval_ws_rows = 0;
+};
+
 namespace gnn {
 namespace host {
+
+// ---- group_eval.hip ------------------------------------------------------------------------------
+void plan_group_eval(gnn_mlp_group *g); // at create: does group_forward_kernel apply to the group's net?
+void free_group_eval(gnn_mlp_group *g);
 
 // ---- error convention (abi.hip) ---------------------------------------------------------------
 int fail(int code, const std::string &msg);   // records the calling thread's message, returns `code`

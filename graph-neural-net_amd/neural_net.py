@@ -407,6 +407,7 @@ class NetGroup:
                                                    _act(last_act), loss, (C.c_int64 * max(1, len(sd)))(*sd), len(sd),
                                                    dtype, device, max_batch, C.byref(self._h)))
         self.layer_dims, self.seeds, self.max_batch = dims, sd, max_batch
+        self._dataset_rows = None
         self.members = []
         for k in range(len(sd)):
             h = C.c_void_p()
@@ -435,6 +436,7 @@ class NetGroup:
         if X.shape[0] != Y.shape[0]:
             raise ValueError("input / expected row counts differ")
         _capi.check(self._lib.gnn_mlp_group_upload_dataset(self._h, _dp(X), _dp(Y), X.shape[0]))
+        self._dataset_rows = X.shape[0]
 
     def upload_dataset_u8(self, pixels, labels):
         pixels = np.ascontiguousarray(pixels, dtype=np.uint8).reshape(-1, self.layer_dims[0])
@@ -444,6 +446,7 @@ class NetGroup:
         u8 = C.POINTER(C.c_uint8)
         _capi.check(self._lib.gnn_mlp_group_upload_dataset_u8(self._h, pixels.ctypes.data_as(u8),
                                                               labels.ctypes.data_as(u8), labels.size))
+        self._dataset_rows = labels.size
 
     def train_range(self, first, B, n_steps, steps, momenta):
         """NetGroup member k: train_range(first, B, n_steps, steps[k], momenta[k]); scalars apply to every member."""
@@ -463,6 +466,47 @@ class NetGroup:
 
     def synchronize(self):
         _capi.check(self._lib.gnn_mlp_group_synchronize(self._h))
+
+    # evaluation of the whole group in one pass (gnn_mlp_group_evaluate_range / _ensemble_range)
+    @property
+    def eval_launches(self):
+        """2: one grouped forward launch + one combine launch per block of rows; 0: member after member."""
+        return self._lib.gnn_mlp_group_eval_launches(self._h)
+
+    def _rows(self, first, n):
+        first = int(first)
+        if n is None:
+            if getattr(self, "_dataset_rows", None) is None:
+                raise ValueError("n=None needs an uploaded data set")
+            n = self._dataset_rows - first
+        return first, int(n)
+
+    def evaluate_range(self, first=0, n=None):
+        """(hits[K], loss_sums[K], ensemble_hits) over rows [first, first + n) of the group's data set: testOnTrainingData
+        (MT:159-197) and the sum of calculateLoss (validate(), NNT:102-113, without its division) for every member, and the
+        hits of the ensemble's mean output."""
+        first, n = self._rows(first, n)
+        k = len(self)
+        hits = np.zeros(k, dtype=np.int64)
+        loss = np.zeros(k, dtype=np.float64)
+        ens = C.c_int64(0)
+        _capi.check(self._lib.gnn_mlp_group_evaluate_range(self._h, first, n, hits.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                           _dp(loss), C.byref(ens)))
+        return hits, loss, int(ens.value)
+
+    def ensemble_propagate_range(self, first, n):
+        """The mean of the members' propagate() over the rows: n x d_out (fp64 of the f32 mean, taken in member order)."""
+        first, n = self._rows(first, n)
+        out = np.empty((max(n, 0), self.layer_dims[-1]), dtype=np.float64)
+        _capi.check(self._lib.gnn_mlp_group_ensemble_range(self._h, first, n, _dp(out), None))
+        return out
+
+    def ensemble_argmax_range(self, first, n):
+        """argmax (MT:166-168) of the mean output, per row."""
+        first, n = self._rows(first, n)
+        lab = np.empty(max(n, 0), dtype=np.int32)
+        _capi.check(self._lib.gnn_mlp_group_ensemble_range(self._h, first, n, None, lab.ctypes.data_as(C.POINTER(C.c_int32))))
+        return lab
 
 
 class DataParallelNeuralNet:

@@ -321,6 +321,17 @@ int gnn_mlp_group_train_sampled(gnn_mlp_group_t *g, gnn_sampler_t *s, int iterat
  * through their own handles (nets off that path, or whose row-block kernel is middle4_kernel) -- same results, no speed-up */
 int gnn_mlp_group_launches_per_step(const gnn_mlp_group_t *g);
 int gnn_mlp_group_synchronize(gnn_mlp_group_t *g);
+/* Evaluation of a whole group in one pass (csrc/group_eval_kernel.h).
+ * 2: one grouped forward launch + one combine launch per block of rows; 0: member after member */
+int gnn_mlp_group_eval_launches(const gnn_mlp_group_t *g);
+/* rows [first, first + n) of the group's data set, any n: member_hits[k] as gnn_mlp_count_hits_range counts them (MT:159-197),
+ * member_loss_sum[k] = sum of calculateLoss over the rows (validate() of NNT:102-113 without its division), *ensemble_hits for the
+ * mean output.  Each of the three may be null, not all of them.  One readback. */
+int gnn_mlp_group_evaluate_range(gnn_mlp_group_t *g, int64_t first, int64_t n, int64_t *member_hits,
+                                 double *member_loss_sum, int64_t *ensemble_hits);
+/* the ensemble's propagate() and argmax over the same rows: mean_out is n x d_out (fp64 of the f32 mean), labels has n entries;
+ * either may be null, not both */
+int gnn_mlp_group_ensemble_range(gnn_mlp_group_t *g, int64_t first, int64_t n, double *mean_out, int32_t *labels);
 
 /* ---- shape specialisation ---------------------------------------------------------------------
  * The per-row-block kernel of the fused small-net path is a template over the net's shape; with
