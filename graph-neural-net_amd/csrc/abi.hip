@@ -143,7 +143,7 @@ int get_flat(gnn_mlp *h, const float *dev, double *flat) {
 }
 int set_flat(gnn_mlp *h, float *dev, const double *flat) {
     if (!flat) return fail(GNN_ERR_BAD_ARG, "null input");
-    if (dev == h->W) h->slab_valid = false; // first-layer sums made with the old weights
+    if (dev == h->W) h->la.weights_replaced();
     std::vector<float> tmp;
     pack_params(h, flat, tmp);
     HIP_TRY(hipMemcpyAsync(dev, tmp.data(), sizeof(float) * (size_t)h->n_pad, hipMemcpyHostToDevice, h->stream));
@@ -396,7 +396,7 @@ int gnn_mlp_gradient_step(gnn_mlp_t *h, const double *X, const double *Y, int B,
         return step_on_host_batch_deferred(h, B, step, momentum);
     }
     TRY(stage_batch(h, X, Y, B));   // the caller's rows are not read after this returns
-    h->have_next = false; // (a hint refers to dataset rows; this batch came from the host)
+    h->la.hint_unused();
     return step_on_rows(h, h->act[0], h->ybuf, B, step, momentum, false);
 }); }
 
@@ -412,7 +412,7 @@ static int alloc_dataset(gnn_mlp *h, int64_t N) { return guarded([&]() -> int {
     if (h->DY) { (void)hipFree(h->DY); h->DY = nullptr; }
     if (h->DXb) { (void)hipFree(h->DXb); h->DXb = nullptr; }
     h->dataset_n = 0;
-    h->slab_valid = false; h->have_next = false; // they name rows of the old dataset
+    h->la.rows_renamed(); // (they name rows of the old dataset)
     const size_t rows = (size_t)N + PAD; // PAD zero rows behind the last sample: a batch's padding rows read them
     TRY(dev_alloc(&h->DX, rows * h->ld[0], h->stream));
     TRY(dev_alloc(&h->DY, rows * h->ld[h->L - 1], h->stream));
@@ -549,12 +549,7 @@ int gnn_mlp_train_range(gnn_mlp_t *h, int64_t first, int B, int n_steps, double 
             if (h->tr_graph) { (void)hipGraphDestroy(h->tr_graph); h->tr_graph = nullptr; }
             if (h->chain) { // two-launch path: the pass is captured as a closed chain -- every step, the last one too, also
                             // makes the first-layer slabs of the batch after it -- so its first batch's slabs must exist before
-                const float *a0 = h->DX + (size_t)(fb * B) * h->ld[0];
-                if (!slabs_hold(h, a0, nullptr, B)) {
-                    const NextBatch self{a0, nullptr, B};
-                    launch_tile_step(h, 0, 0, &self, a0, B, 0.f, 0.f);
-                    slabs_now_hold(h, self, false);
-                }
+                ensure_slabs(h, NextBatch{h->DX + (size_t)(fb * B) * h->ld[0], nullptr, B});
             }
             if (hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
                 const int t0 = h->time;
@@ -580,12 +575,7 @@ int gnn_mlp_train_range(gnn_mlp_t *h, int64_t first, int B, int n_steps, double 
             }
         }
         if (h->tr_exec && h->chain && n_steps - s >= nb) { // a replay starts from batch fb's slabs and leaves them behind again
-            const float *a0 = h->DX + (size_t)(fb * B) * h->ld[0];
-            if (!slabs_hold(h, a0, nullptr, B)) {
-                const NextBatch self{a0, nullptr, B};
-                launch_tile_step(h, 0, 0, &self, a0, B, 0.f, 0.f);
-                slabs_now_hold(h, self, false);
-            }
+            ensure_slabs(h, NextBatch{h->DX + (size_t)(fb * B) * h->ld[0], nullptr, B});
         }
         while (h->tr_exec && n_steps - s >= nb) {
             HIP_TRY(hipGraphLaunch(h->tr_exec, h->stream));
@@ -605,7 +595,7 @@ int gnn_mlp_gradient_step_indexed(gnn_mlp_t *h, const int32_t *idx, int B, doubl
     for (int i = 0; i < B; i++)
         if (idx[i] < 0 || idx[i] >= h->dataset_n) return fail(GNN_ERR_BAD_ARG, "sample index out of range");
     HIP_TRY(hipMemcpyAsync(h->idxbuf, idx, sizeof(int32_t) * (size_t)B, hipMemcpyHostToDevice, h->stream));
-    h->slab_valid = false; h->have_next = false; // idxbuf is reused: its address does not identify a batch
+    h->la.rows_renamed(); // (idxbuf is reused: its address does not identify a batch)
     return step_on_device_indices(h, h->idxbuf, B, step, momentum);
 }); }
 
@@ -709,14 +699,9 @@ int gnn_mlp_apply_update(gnn_mlp_t *h, int B_global, double step, double momentu
     TRY(check_handle(h));
     if (B_global <= 0) return fail(GNN_ERR_BAD_ARG, "B_global must be positive");
     if (!(step > 0)) return fail(GNN_ERR_BAD_ARG, "step must be positive (SCE:301)");
-    NextBatch nb{};
-    if (h->chain && take_next(h, &nb)) {
-        // the update by weight tiles, each tile going straight on to the next batch's first-layer slab
-        launch_tile_step(h, 2, 2, &nb, nullptr, PAD, (float)(step / (double)B_global), (float)momentum);
-        slabs_now_hold(h, nb, nb.idx != nullptr);
-    } else {
+    if (!update_by_tiles(h, 2, (float)(step / (double)B_global), (float)momentum)) {
         launch_flat_update(h, B_global, step, momentum);
-        h->slab_valid = false; h->have_next = false;
+        h->la.rows_renamed();
     }
     h->time++;
     TRY_LAUNCHES(h);
@@ -725,7 +710,7 @@ int gnn_mlp_apply_update(gnn_mlp_t *h, int B_global, double step, double momentu
 
 int gnn_mlp_forget_lookahead(gnn_mlp_t *h) { return guarded([&]() -> int {
     if (!h) return fail(GNN_ERR_BAD_ARG, "null handle");
-    h->slab_valid = false; h->have_next = false; h->xstage_valid = false;
+    h->la.forget();
     return GNN_OK;
 }); }
 

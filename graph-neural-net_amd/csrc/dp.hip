@@ -149,15 +149,12 @@ int dp_reduce_and_update(gnn_mlp_dp *d, int B_global, double step, double moment
         const bool rs = d->reducer == GNN_REDUCE_DIRECT_RS;
         for (int j = 0; j < n; j++)
             if (j != r) HIP_TRY(hipStreamWaitEvent(h->stream, rs ? d->scat_done[j] : d->grad_done[par][j], 0));
-        NextBatch nb{};
-        if (h->chain && take_next(h, &nb)) {
-            // by weight tiles: each tile's sum (or gather) -> update -> the next batch's first-layer slab, one launch
-            PeerGradients pg{};
-            for (int j = 0; j < n; j++) pg.G[j] = rs ? d->red[j] : d->gbuf[par][j];
-            pg.n = n; pg.slice = (unsigned)d->slice;
-            launch_tile_step(h, rs ? 4 : 3, 2, &nb, nullptr, PAD, sob, mom, false, &pg);
-            slabs_now_hold(h, nb, nb.idx != nullptr);
-        } else if (rs) {
+        // by weight tiles: each tile's sum (or gather) -> update -> the next batch's first-layer slab, one launch
+        PeerGradients pg{};
+        for (int j = 0; j < n; j++) pg.G[j] = rs ? d->red[j] : d->gbuf[par][j];
+        pg.n = n; pg.slice = (unsigned)d->slice;
+        const bool by_tiles = update_by_tiles(h, rs ? 4 : 3, sob, mom, &pg);
+        if (!by_tiles && rs) {
             DirectGatherParams p{};
             for (int j = 0; j < n; j++) p.red[j] = reinterpret_cast<const float4 *>(d->red[j]);
             p.n = n; p.slice4 = d->slice / 4;
@@ -166,8 +163,7 @@ int dp_reduce_and_update(gnn_mlp_dp *d, int B_global, double step, double moment
             p.n4 = h->n_pad / 4;
             p.step_over_b = sob; p.momentum = mom;
             launch_timed(h, GNN_K_UPDATE, direct_gather_update_kernel, dim3(grid_for(p.n4)), dim3(256), 0, p);
-            h->slab_valid = false; h->have_next = false;
-        } else {
+        } else if (!by_tiles) {
             DirectReduceParams p{};
             for (int j = 0; j < n; j++) p.G[j] = reinterpret_cast<const float4 *>(d->gbuf[par][j]);
             p.n = n;
@@ -176,8 +172,8 @@ int dp_reduce_and_update(gnn_mlp_dp *d, int B_global, double step, double moment
             p.n4 = h->n_pad / 4;
             p.step_over_b = sob; p.momentum = mom;
             launch_timed(h, GNN_K_UPDATE, direct_reduce_update_kernel, dim3(grid_for(p.n4)), dim3(256), 0, p);
-            h->slab_valid = false; h->have_next = false;
         }
+        if (!by_tiles) h->la.rows_renamed();
         HIP_TRY(hipEventRecord(d->red_done[par][r], h->stream));
     }
     // every replica's update is enqueued: one check over all of them, then the step counts for all or for none
@@ -287,13 +283,9 @@ int gnn_mlp_rccl_train_range(gnn_mlp_t *h, int64_t first, int B_local, int n_ste
         if (rc) return dp_rccl_fail(rc, "ncclAllReduce");
         // (3) the identical update on every rank (SCE:327-342 with batchSize = B_global), by weight tiles, each tile going on to
         //     the next batch's first-layer slab where the net takes the two-launch path
-        NextBatch nb_next{};
-        if (h->chain && take_next(h, &nb_next)) {
-            launch_tile_step(h, 2, 2, &nb_next, nullptr, PAD, sob, mom);
-            slabs_now_hold(h, nb_next, nb_next.idx != nullptr);
-        } else {
+        if (!update_by_tiles(h, 2, sob, mom)) {
             launch_flat_update(h, B_global, step, momentum);
-            h->slab_valid = false; h->have_next = false;
+            h->la.rows_renamed();
         }
         h->time++;
         TRY_LAUNCHES(h);

@@ -26,49 +26,22 @@ void free_group(gnn_mlp_group *g) {
     delete g;
 }
 
-// the look-ahead state of a handle (handle.h: slabs / next batch / staged rows), with the pointers that name member 0's
-// buffers moved to member k's
-struct Lookahead {
-    bool slab_valid, have_next, xstage_valid;
-    const float *slab_a0, *next_a0; const int32_t *slab_idx, *next_idx;
-    int slab_B, next_B, xstage_cur;
-    bool operator==(const Lookahead &o) const {
-        return slab_valid == o.slab_valid && have_next == o.have_next && xstage_valid == o.xstage_valid && slab_a0 == o.slab_a0 &&
-               next_a0 == o.next_a0 && slab_idx == o.slab_idx && next_idx == o.next_idx && slab_B == o.slab_B &&
-               next_B == o.next_B && xstage_cur == o.xstage_cur;
-    }
-};
-template <class T> T *moved(const gnn_mlp_group *g, T *p, int k) {
-    const char *lo = g->arena;
-    if (!p || (size_t)(reinterpret_cast<const char *>(p) - lo) >= g->S) return p;
-    return reinterpret_cast<T *>(reinterpret_cast<uintptr_t>(p) + (uintptr_t)k * g->S);
-}
-Lookahead lookahead_of(const gnn_mlp_group *g, const gnn_mlp *h, int k) {
-    return Lookahead{h->slab_valid, h->have_next, h->xstage_valid, moved(g, h->slab_a0, k), moved(g, h->next_a0, k),
-                     moved(g, h->slab_idx, k), moved(g, h->next_idx, k), h->slab_B, h->next_B, h->xstage_cur};
-}
-void set_lookahead(gnn_mlp *h, const Lookahead &a) {
-    h->slab_valid = a.slab_valid; h->have_next = a.have_next; h->xstage_valid = a.xstage_valid;
-    h->slab_a0 = a.slab_a0; h->next_a0 = a.next_a0; h->slab_idx = a.slab_idx; h->next_idx = a.next_idx;
-    h->slab_B = a.slab_B; h->next_B = a.next_B; h->xstage_cur = a.xstage_cur;
-}
-
-// Before a grouped call: every member's deferred update is applied, and member 0's look-ahead state -- which the grouped
-// launches act on for everyone -- must describe every member.  If it does not (a member was stepped alone), all of it is
-// dropped: gnn_mlp_forget_lookahead keeps results bitwise, it only costs a forward-only launch.
+// Before a grouped call: every member's deferred update is applied, and member 0's look-ahead state (lookahead.h) -- which the
+// grouped launches act on for everyone -- must describe every member.  If it does not (a member was stepped alone), all of it
+// is dropped: forgetting keeps results bitwise, it only costs a forward-only launch.
 int enter_grouped(gnn_mlp_group *g) {
     for (gnn_mlp *h : g->m) TRY(check_handle(h));
     bool same = true;
-    for (int k = 1; k < g->K && same; k++) same = lookahead_of(g, g->m[0], k) == lookahead_of(g, g->m[k], 0);
+    for (int k = 1; k < g->K && same; k++) same = g->m[0]->la.rebased(g->arena, g->S, k) == g->m[k]->la;
     if (!same)
-        for (gnn_mlp *h : g->m) { h->slab_valid = false; h->have_next = false; h->xstage_valid = false; h->xstage_cur = g->m[0]->xstage_cur; }
+        for (int k = 0; k < g->K; k++) { g->m[k]->la = g->m[0]->la.rebased(g->arena, g->S, k); g->m[k]->la.forget(); } // (one staging buffer index for all)
     return GNN_OK;
 }
 // After it: member 0's step count and look-ahead state, moved to each member
 void leave_grouped(gnn_mlp_group *g, int steps_done) {
     for (int k = 1; k < g->K; k++) {
         g->m[k]->time += steps_done;
-        set_lookahead(g->m[k], lookahead_of(g, g->m[0], k));
+        g->m[k]->la = g->m[0]->la.rebased(g->arena, g->S, k);
     }
 }
 
@@ -182,7 +155,7 @@ static int share_dataset(gnn_mlp_group *g) {
         gnn_mlp *h = g->m[k];
         h->DX = h0->DX; h->DY = h0->DY; h->DXb = h0->DXb; h->dataset_n = h0->dataset_n;
         h->shared_dataset = true;
-        h->slab_valid = false; h->have_next = false; // (they name rows of the old dataset)
+        h->la.rows_renamed(); // (they name rows of the old dataset)
     }
     return GNN_OK;
 }

@@ -13,6 +13,7 @@
 #include "group_eval_kernel.h"
 #include "kernels.h"
 #include "eval_kernels.h"
+#include "lookahead.h"
 
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
@@ -108,15 +109,10 @@ struct gnn_mlp {
     float *slabs = nullptr;
     int n_slabs = 0;
     std::string plan_note;    // why the net is NOT on the two-launch path (empty when it is): gnn_mlp_plan_note
-    // the batch whose first-layer sums (for the CURRENT weights) the slabs hold
-    bool slab_valid = false; const float *slab_a0 = nullptr; const int32_t *slab_idx = nullptr; int slab_B = 0;
-    // the batch the next gradient computation will run on (gnn_mlp_hint_next_range, train loops); consumed by the
-    // next kernel that updates the weights
-    bool have_next = false; const float *next_a0 = nullptr; const int32_t *next_idx = nullptr; int next_B = 0;
+    gnn::host::Lookahead la;  // what the slabs hold, the announced next batch, which staging buffer is current (lookahead.h)
     // contiguous copies of SAMPLED batches (two, used alternately): the tile kernel that forms a sampled batch's slabs also
     // writes the rows it gathered; the next step's gradient product reads them in place of the index-gathered rows
     float *xstage[2] = {nullptr, nullptr}; __bf16 *xstage_b[2] = {nullptr, nullptr};
-    int xstage_cur = 0; bool xstage_valid = false; // xstage[xstage_cur] holds the rows of the batch the slabs describe
     int specialization = 0;   // 0 runtime-shape kernels, 1 prebuilt static shape, 2 run-time instantiation
     bool jit_tried = false;
     int steps_seen = 0;       // gradient computations so far: the 16th triggers the specialisation
@@ -354,7 +350,6 @@ void backward_bf16(gnn_mlp *h, const __bf16 *a0b, int B, bool fused_update, floa
 void to_bf16(gnn_mlp *h, const float *src, __bf16 *dst, size_t n);
 
 // ---- launch_small.hip: the row-block kernel and the tile-owner kernel ----------------------------
-struct NextBatch { const float *a0; const int32_t *idx; int B; };
 // which rows the row-block kernel copies to a staging buffer while its row tail runs (RbParams::xcopy): none, its own
 // sampled batch's (to xstage[xstage_cur]), or the announced NEXT sampled batch's (to the other buffer)
 enum { RB_COPY_NONE = 0, RB_COPY_CURRENT = 1, RB_COPY_NEXT = 2 };
@@ -396,9 +391,8 @@ void launch_flat_update(gnn_mlp *h, int B_global, double step, double momentum);
 void plan_fused(gnn_mlp *h);
 void plan_chain(gnn_mlp *h);
 const __bf16 *a0_bf16(const gnn_mlp *h, const float *a0);
-bool slabs_hold(const gnn_mlp *h, const float *a0, const int32_t *idx, int B);
-bool take_next(gnn_mlp *h, NextBatch *nb);
-void slabs_now_hold(gnn_mlp *h, const NextBatch &nb, bool staged_copy = false, bool by_rowblock = false);
+void ensure_slabs(gnn_mlp *h, const NextBatch &batch);
+bool update_by_tiles(gnn_mlp *h, int gsrc, float step_over_b, float momentum, const PeerGradients *peers = nullptr);
 void hint_range(gnn_mlp *h, int64_t row0, int B);
 void do_forward(gnn_mlp *h, const float *a0, const float *y, int B, bool want_prob, bool want_loss, bool want_label);
 void do_gradient(gnn_mlp *h, const float *a0, const float *y, int B, bool fused_update, float step_over_b, float momentum,

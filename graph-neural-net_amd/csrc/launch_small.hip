@@ -163,12 +163,12 @@ void fused_forward(gnn_mlp *h, const float *a0, const float *y, int B, bool back
         r.row_idx = h->cur_idx;
         if (copy_rows == RB_COPY_CURRENT && h->cur_idx) { // the sampled batch's rows, contiguous, for the tile kernel that follows (RbParams::xcopy)
             r.ldx = h->ld[0]; r.copy_idx = h->cur_idx;
-            if (h->dtype == GNN_DTYPE_BF16) { r.Xb = a0_bf16(h, a0); r.xcopyb = h->xstage_b[h->xstage_cur]; }
-            else { r.X = a0; r.xcopy = h->xstage[h->xstage_cur]; }
-        } else if (copy_rows == RB_COPY_NEXT && h->have_next && h->next_idx) { // the announced next batch's rows, to the OTHER buffer
-            r.ldx = h->ld[0]; r.copy_idx = h->next_idx; // (next_B == B: chain_gradient)
-            if (h->dtype == GNN_DTYPE_BF16) { r.Xb = a0_bf16(h, h->next_a0); r.xcopyb = h->xstage_b[h->xstage_cur ^ 1]; }
-            else { r.X = h->next_a0; r.xcopy = h->xstage[h->xstage_cur ^ 1]; }
+            if (h->dtype == GNN_DTYPE_BF16) { r.Xb = a0_bf16(h, a0); r.xcopyb = h->xstage_b[h->la.xstage_cur]; }
+            else { r.X = a0; r.xcopy = h->xstage[h->la.xstage_cur]; }
+        } else if (copy_rows == RB_COPY_NEXT && h->la.have_next && h->la.next.idx) { // the announced next batch's rows, to the OTHER buffer
+            r.ldx = h->ld[0]; r.copy_idx = h->la.next.idx; // (next_B == B: chain_gradient)
+            if (h->dtype == GNN_DTYPE_BF16) { r.Xb = a0_bf16(h, h->la.next.a0); r.xcopyb = h->xstage_b[h->la.xstage_cur ^ 1]; }
+            else { r.X = h->la.next.a0; r.xcopy = h->xstage[h->la.xstage_cur ^ 1]; }
         }
         // (the head arguments: rowblock_kernel.h, GNN_RB_HEAD_PARAMS -- in this order)
         const bool bf = h->dtype == GNN_DTYPE_BF16; // (the bf16 kernel takes its bf16 shadows' pointers in the two weight slots)
@@ -241,11 +241,11 @@ void launch_tile_step(gnn_mlp *h, int gsrc, int gdst, const NextBatch *next, con
         for (int r = 0; r < peers->n; r++) t.Gpeer[r] = peers->G[r];
         t.n_peer = peers->n; t.slice = peers->slice; t.Gself = h->G;
     }
-    t.layer[0].A = staged ? h->xstage[h->xstage_cur] : a0;
+    t.layer[0].A = staged ? h->xstage[h->la.xstage_cur] : a0;
     for (int l = 0; l < t.n_layers; l++) t.layer[l].G = h->G + h->w_off[l];
     t.K = pad_up(B); t.k_true = B;
     t.row_idx = staged ? nullptr : h->cur_idx;
-    const int stage_dst = h->xstage_cur ^ 1; // a sampled next batch is copied to the OTHER buffer (this launch may be reading the current one)
+    const int stage_dst = h->la.xstage_cur ^ 1; // a sampled next batch is copied to the OTHER buffer (this launch may be reading the current one)
     if (next && next->idx && !h->rb) { t.stage_out = h->xstage[stage_dst]; t.stage_out_b = h->xstage_b[stage_dst]; } // (with the row-block kernel on the path IT makes the copy)
     t.step_over_b = step_over_b; t.momentum = momentum;
     const bool fwd = next != nullptr;
@@ -259,7 +259,7 @@ void launch_tile_step(gnn_mlp *h, int gsrc, int gdst, const NextBatch *next, con
     if (h->ts_map_args) std::memcpy(t.map_words, h->ts_map_words[fwd_only ? 1 : 0], sizeof(t.map_words));
     const int cls = fwd_only ? GNN_K_FWD_GEMM0 : gsrc >= 2 ? GNN_K_UPDATE : GNN_K_GRAD_GEMM0;
     if (h->dtype == GNN_DTYPE_BF16) {
-        if (staged) t.Ab[0] = h->xstage_b[h->xstage_cur];
+        if (staged) t.Ab[0] = h->xstage_b[h->la.xstage_cur];
         else if (a0) t.Ab[0] = a0_bf16(h, a0);
         if (fwd) t.Anb = next_staged ? h->xstage_b[stage_dst] : a0_bf16(h, next->a0);
     }

@@ -143,58 +143,53 @@ void plan_chain(gnn_mlp *h) {
     h->chain = true;
 }
 
-bool slabs_hold(const gnn_mlp *h, const float *a0, const int32_t *idx, int B) {
-    return h->slab_valid && h->slab_a0 == a0 && h->slab_idx == idx && h->slab_B == B;
+// (on the row-block kernel's path the tile kernel writes no staged copy: that kernel does, by_rowblock)
+static void slabs_now_hold(gnn_mlp *h, const NextBatch &nb, bool staged_copy, bool by_rowblock = false) {
+    h->la.slabs_now_hold(nb, staged_copy && (!h->rb || by_rowblock));
 }
-// the hint is good for ONE weight update
-bool take_next(gnn_mlp *h, NextBatch *nb) {
-    if (!h->have_next) return false;
-    h->have_next = false;
-    *nb = NextBatch{h->next_a0, h->next_idx, h->next_B};
+// Chain start: unless the slabs hold `batch` already, a forward-only launch makes them from the weights as they are
+void ensure_slabs(gnn_mlp *h, const NextBatch &batch) {
+    if (h->la.slabs_hold(batch)) return;
+    launch_tile_step(h, 0, 0, &batch, batch.a0, batch.B, 0.f, 0.f);
+    slabs_now_hold(h, batch, batch.idx != nullptr);
+}
+// The update from the gradient buffer(s) by weight tiles (gsrc 2: G; 3 / 4: the peers'), each tile going straight on to the announced batch's
+// first-layer slab.  False, nothing launched, off the two-launch path or with nothing announced: the caller's own update kernel, then la.rows_renamed()
+bool update_by_tiles(gnn_mlp *h, int gsrc, float step_over_b, float momentum, const PeerGradients *peers) {
+    NextBatch nb{};
+    if (!h->chain || !h->la.take_next(&nb)) return false;
+    launch_tile_step(h, gsrc, 2, &nb, nullptr, PAD, step_over_b, momentum, false, peers);
+    slabs_now_hold(h, nb, nb.idx != nullptr);
     return true;
-}
-// staged_copy: the launch that made these slabs also wrote the batch's rows to the other staging buffer
-void slabs_now_hold(gnn_mlp *h, const NextBatch &nb, bool staged_copy, bool by_rowblock) {
-    if (h->rb && !by_rowblock) staged_copy = false; // (on the row-block kernel's path the tile kernel writes no copy: that kernel does)
-    h->slab_valid = true; h->slab_a0 = nb.a0; h->slab_idx = nb.idx; h->slab_B = nb.B;
-    if (staged_copy) h->xstage_cur ^= 1;
-    h->xstage_valid = staged_copy;
 }
 
 // One gradient computation on the two-launch path.  `resident`: the rows live in the dataset (a staging
 // buffer holds other data under the same address at the next call, so its slabs are never reused).
 void chain_gradient(gnn_mlp *h, const float *a0, const float *y, int B, bool fused_update, float step_over_b, float momentum, bool resident) {
-    if (!slabs_hold(h, a0, h->cur_idx, B)) {
-        const NextBatch self{a0, h->cur_idx, B};
-        launch_tile_step(h, 0, 0, &self, a0, B, 0.f, 0.f); // chain start: the slabs of this batch from the weights as they are
-        slabs_now_hold(h, self, self.idx != nullptr);
-    }
+    Lookahead &la = h->la;
+    const NextBatch self{a0, h->cur_idx, B};
+    ensure_slabs(h, self);
     // A sampled batch on the row-block kernel's path: that kernel makes the contiguous copies the tile kernel reads with plain
     // addressing.  In a training loop that announces its next batch (train_sampled) it copies the NEXT batch's rows: the tile
     // kernel's first-layer product reads them without an index -> address -> row chain at its top (7.25 -> 5.6 us per launch at
     // 784-300-100-10), and one step later the same copy is the gradient operand.  Without an announced sampled batch of the same
     // size it copies its own rows, for the gradient product only (the first step of a chain gathers that operand by index).
-    const bool have_copy = h->xstage_valid && h->cur_idx != nullptr; // (made one step ago, or by the tile launch that made the slabs)
-    const bool rb_next = h->rb && fused_update && h->have_next && h->next_idx != nullptr && h->next_B == B;
+    const bool have_copy = la.xstage_valid && h->cur_idx != nullptr; // (made one step ago, or by the tile launch that made the slabs)
+    const bool rb_next = h->rb && fused_update && la.have_next && la.next.idx != nullptr && la.next.B == B;
     const bool rb_cur = h->rb && !rb_next && !have_copy && h->cur_idx != nullptr;
     const bool staged = have_copy || rb_cur;
-    h->slab_valid = false;
+    la.step_takes_slabs();
     fused_forward(h, a0, y, B, true, false, false, false, true, rb_next ? RB_COPY_NEXT : rb_cur ? RB_COPY_CURRENT : RB_COPY_NONE);
     NextBatch nb{};
     if (fused_update) {
-        const bool fwd = take_next(h, &nb);
+        const bool fwd = la.take_next(&nb);
         launch_tile_step(h, 1, 2, fwd ? &nb : nullptr, a0, B, step_over_b, momentum, staged, nullptr, rb_next);
         if (fwd) slabs_now_hold(h, nb, rb_next || nb.idx != nullptr, rb_next);
-        else h->xstage_valid = false;
+        else la.step_left_no_slabs();
     } else {
         launch_tile_step(h, 1, 1, nullptr, a0, B, 0.f, 0.f, staged);
-        if (resident) { // weights unchanged: the slabs (and the staged rows) still describe this batch
-            const bool keep = staged;
-            slabs_now_hold(h, NextBatch{a0, h->cur_idx, B});
-            h->xstage_valid = keep;
-        } else {
-            h->xstage_valid = false;
-        }
+        if (resident) la.step_kept_weights(self, staged);
+        else la.step_left_no_slabs();
     }
 }
 
@@ -260,7 +255,7 @@ void do_forward(gnn_mlp *h, const float *a0, const float *y, int B, bool want_pr
 void do_gradient(gnn_mlp *h, const float *a0, const float *y, int B, bool fused_update, float step_over_b, float momentum,
                  bool resident) {
     if (h->chain) { chain_gradient(h, a0, y, B, fused_update, step_over_b, momentum, resident); return; }
-    h->have_next = false;
+    h->la.hint_unused();
     if (h->dtype == GNN_DTYPE_BF16) {
         const __bf16 *a0b = a0_bf16(h, a0);
         const bool tail = use_tail(h); // last layer + output rule + delta_{L-2} in one launch (three of the twelve of configs[4])
@@ -377,7 +372,7 @@ void flush_pending_update(gnn_mlp *h) {
     h->pend.on = false;
     h->cur_idx = nullptr;
     launch_tile_step(h, 1, 2, nullptr, h->act[0], h->pend.B, h->pend.step_over_b, h->pend.momentum);
-    h->slab_valid = false; h->have_next = false; h->xstage_valid = false;
+    h->la.forget();
 }
 
 // One gradientStep on the batch staged in act[0] / ybuf: (update of the PENDING step + this batch's first-layer sums) in one
@@ -388,7 +383,7 @@ int step_on_host_batch_deferred(gnn_mlp *h, int B, double step, double momentum)
     maybe_specialize(h);
     const float *a0 = h->act[0];
     h->cur_idx = nullptr;
-    h->have_next = false; // (a hint refers to dataset rows; this batch came from the host)
+    h->la.hint_unused();
     const NextBatch self{a0, nullptr, B};
     if (h->pend.on) {
         h->pend.on = false;
@@ -396,7 +391,7 @@ int step_on_host_batch_deferred(gnn_mlp *h, int B, double step, double momentum)
     } else {
         launch_tile_step(h, 0, 0, &self, a0, B, 0.f, 0.f);
     }
-    h->slab_valid = false; h->xstage_valid = false; // (a staging buffer holds other rows under the same address at the next call)
+    h->la.slabs_of_staging_buffer();
     fused_forward(h, a0, h->ybuf, B, true, false, false, false, true, RB_COPY_NONE);
     h->pend.on = true; h->pend.B = B; h->pend.step_over_b = (float)(step / (double)B); h->pend.momentum = (float)momentum;
     h->time++;
@@ -406,7 +401,7 @@ int step_on_host_batch_deferred(gnn_mlp *h, int B, double step, double momentum)
 
 // the next gradient computation runs on dataset rows [row0, row0 + B)
 void hint_range(gnn_mlp *h, int64_t row0, int B) {
-    h->have_next = true; h->next_a0 = h->DX + (size_t)row0 * h->ld[0]; h->next_idx = nullptr; h->next_B = B;
+    h->la.announce(NextBatch{h->DX + (size_t)row0 * h->ld[0], nullptr, B});
 }
 
 int step_on_device_indices(gnn_mlp *h, const int32_t *d_idx, int B, double step, double momentum) {

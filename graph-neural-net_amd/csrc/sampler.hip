@@ -287,10 +287,10 @@ static int train_sampled_impl(gnn_mlp_t *h, gnn_sampler_t *s, int iterations, in
         const int *ccnt = dcnt.data() + (size_t)(c % kRing) * kChunk;
         for (int i = i0; i < i1 && rc == GNN_OK; i++) {
             if (h->chain && i + 1 < i1) { // the next draw of this chunk is already on the device
-                h->have_next = true; h->next_a0 = h->DX; h->next_idx = d_idx + so + (size_t)(i + 1 - i0) * batch; h->next_B = ccnt[i + 1 - i0];
+                h->la.announce(NextBatch{h->DX, d_idx + so + (size_t)(i + 1 - i0) * batch, ccnt[i + 1 - i0]});
             } else if (h->chain && uploaded > c + 1) { // ... and so is the first draw of the next chunk
                 const size_t sn = (size_t)((c + 1) % kRing) * slot_elems;
-                h->have_next = true; h->next_a0 = h->DX; h->next_idx = d_idx + sn; h->next_B = dcnt[(size_t)((c + 1) % kRing) * kChunk];
+                h->la.announce(NextBatch{h->DX, d_idx + sn, dcnt[(size_t)((c + 1) % kRing) * kChunk]});
             }
             rc = step_on_device_indices(h, d_idx + so + (size_t)(i - i0) * batch, ccnt[i - i0], step, momentum);
             // (the validation pass reads the weights the step has just written; it touches neither the slabs the step's tile
@@ -306,7 +306,7 @@ static int train_sampled_impl(gnn_mlp_t *h, gnn_sampler_t *s, int iterations, in
     }
     // (on an early exit the sampler stops after the chunk it is drawing: its state stays well defined)
     (void)hipStreamSynchronize(h->stream); // the device ring is released below
-    h->slab_valid = false; h->have_next = false; // (they may name rows through d_idx)
+    h->la.rows_renamed(); // (they may name rows through d_idx)
     return rc;
 }
 
