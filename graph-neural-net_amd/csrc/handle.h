@@ -1,5 +1,6 @@
 // handle.h -- internal: the handle behind gnn_mlp_t, the error convention, and the functions the
-// translation units of the library call in each other (abi / plan / launch_* / checkpoint / sampler / dp).
+// translation units of the library call in each other (abi / plan / launch_* / checkpoint / sampler / dp), the timers' slots
+// (timer_slot) and the one launcher of a kernel instance held as a pointer (launch_instance; the instances: instances.h).
 // Nothing here is part of the C ABI (include/gnn_mlp.h).
 #pragma once
 #include "../../include/gnn_mlp.h"
@@ -14,6 +15,7 @@
 #include "kernels.h"
 #include "eval_kernels.h"
 #include "lookahead.h"
+#include "timer_slots.h"
 
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
@@ -25,10 +27,7 @@
 #include <string>
 #include <vector>
 
-struct TimerClass {
-    std::vector<hipEvent_t> start, stop;
-    size_t used = 0;
-};
+using TimerClass = gnn::host::TimerSlots<hipEvent_t>;
 
 namespace gnn {
 namespace host {
@@ -252,24 +251,19 @@ inline int grid_for(int64_t n) {
     return (int)b;
 }
 
-// ---- timing ---------------------------------------------------------------------------
-struct ScopedTimer {
-    gnn_mlp *h; int cls; bool on = false; size_t slot = 0;
-    ScopedTimer(gnn_mlp *h_, int c) : h(h_), cls(c) {
-        if (!h->timing) return;
-        TimerClass &t = h->timers[cls];
-        if (t.used >= 8192) return;
-        if (t.used >= t.start.size()) {
-            hipEvent_t a, b;
-            if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) return;
-            t.start.push_back(a); t.stop.push_back(b);
-        }
-        slot = t.used++;
-        on = true;
-        (void)hipEventRecord(t.start[slot], h->stream);
+// ---- timing and launches ----------------------------------------------------------------
+// the next timer slot of class `cls` (timer_slots.h): false when timing is off, cls < 0 (or past the last class), the class is full or an event cannot be created
+inline bool timer_slot(gnn_mlp *h, int cls, hipEvent_t *ev0, hipEvent_t *ev1) {
+    return take_timer_slot(h->timing, h->timers, cls, [](hipEvent_t *e) { return hipEventCreate(e) == hipSuccess; }, ev0, ev1);
+}
+
+struct ScopedTimer { // events recorded around a stretch of the stream
+    gnn_mlp *h; hipEvent_t ev0 = nullptr, ev1 = nullptr; bool on;
+    ScopedTimer(gnn_mlp *h_, int cls) : h(h_), on(timer_slot(h_, cls, &ev0, &ev1)) {
+        if (on) (void)hipEventRecord(ev0, h->stream);
     }
     ~ScopedTimer() {
-        if (on) (void)hipEventRecord(h->timers[cls].stop[slot], h->stream);
+        if (on) (void)hipEventRecord(ev1, h->stream);
     }
 };
 
@@ -277,21 +271,27 @@ struct ScopedTimer {
 // elapsed time between them is the kernel's execution time, the same quantity rocprofv3's
 // kernel trace reports -- unlike events recorded around a launch, which add marker overhead.
 template <class K, class... P> void launch_timed(gnn_mlp *h, int cls, K kernel, dim3 grid, dim3 block, size_t lds, const P &...params) {
-    if (h->timing && cls >= 0) {
-        TimerClass &t = h->timers[cls];
-        if (t.used < 8192) {
-            if (t.used >= t.start.size()) {
-                hipEvent_t a = nullptr, b = nullptr;
-                if (hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess) { t.start.push_back(a); t.stop.push_back(b); }
-            }
-            if (t.used < t.start.size()) {
-                const size_t slot = t.used++;
-                hipExtLaunchKernelGGL(kernel, grid, block, (uint32_t)lds, h->stream, t.start[slot], t.stop[slot], 0, params...);
-                return;
-            }
-        }
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    if (timer_slot(h, cls, &ev0, &ev1)) hipExtLaunchKernelGGL(kernel, grid, block, (uint32_t)lds, h->stream, ev0, ev1, 0, params...);
+    else hipLaunchKernelGGL(kernel, grid, block, lds, h->stream, params...);
+}
+
+// The launch of an instance held as a POINTER (instances.h; `args` as hipLaunchKernel takes them), timed like launch_timed:
+// the run-time instantiation `module_fn` when set (jit.h; a module launch gives its global size in threads), else `fn`.
+// A refused launch must not pass for a step: the first one since the last check goes to h->launch_error (check_launches);
+// a null instance -- a form its family does not have -- is a refused launch.
+inline void launch_instance(gnn_mlp *h, int cls, const void *fn, hipFunction_t module_fn, dim3 grid, dim3 block, size_t lds, void **args) {
+    if (!fn && !module_fn) { // (before a timer slot is taken: its events would never be recorded)
+        if (h->launch_error == hipSuccess) h->launch_error = hipErrorInvalidValue;
+        return;
     }
-    hipLaunchKernelGGL(kernel, grid, block, lds, h->stream, params...);
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    const bool timed = timer_slot(h, cls, &ev0, &ev1);
+    hipError_t le;
+    if (module_fn) le = hipExtModuleLaunchKernel(module_fn, grid.x * block.x, grid.y * block.y, grid.z * block.z, block.x, block.y, block.z, lds, h->stream, args, nullptr, ev0, ev1, 0);
+    else if (timed) le = hipExtLaunchKernel(const_cast<void *>(fn), grid, block, args, lds, h->stream, ev0, ev1, 0);
+    else le = hipLaunchKernel(fn, grid, block, args, lds, h->stream);
+    if (le != hipSuccess && h->launch_error == hipSuccess) h->launch_error = le;
 }
 
 // More than 64 KB of dynamic LDS needs hipFuncAttributeMaxDynamicSharedMemorySize -- per kernel AND per device (a handle over N
@@ -365,7 +365,6 @@ void launch_tile_step(gnn_mlp *h, int gsrc, int gdst, const NextBatch *next, con
 
 // ---- group_kernels.hip / group_kernels_gnn.hip: the grouped instances ----------------------------------
 const void *rb_group_function(const gnn_mlp *h); // the grouped row-block kernel of h's net, or null (h->rb must hold)
-const void *rb_group_static_general(int which, int act, bool bf);
 // the launches of launch_small.hip for every member of h->grp: member 0's arguments, one grid row per member
 void launch_tile_step_group(gnn_mlp *h, int gsrc, int gdst, bool fwd, unsigned grid, const TileStepParams &t, int B);
 void launch_rowblock_group(gnn_mlp *h, unsigned grid, void *const *head_and_params); // (GNN_RB_HEAD_PARAMS + the RbParams)

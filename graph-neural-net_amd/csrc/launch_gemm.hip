@@ -1,6 +1,6 @@
 // launch_gemm.hip -- host side of the per-layer f32 GEMM path (kernels.h, gemm_wavek.h) and of the three-launch
 // small-net kernels (fused_kernels.h): tile choice and launches.
-#include "handle.h"
+#include "instances.h"
 #include "gemm_f32_dma.h"
 
 using namespace gnn;
@@ -227,25 +227,11 @@ void launch_fwd_first(gnn_mlp *h, const float *a0, int B) {
     // else 8: waves are launched at ~2 100 per us chip-wide, so at this size halving the wave count
     // is worth more than the shorter per-wave chain (4.2 vs 4.6 us at 784x300, B = 128)
     const dim3 fg(f.tiling.blocks());
-    if (f.K / 16 <= 4 * 13) {
-        const dim3 fb(4 * 64);
-        switch (h->inner_act) {
-        case 0: launch_timed(h, GNN_K_FWD_GEMM0, fwd_first_kernel<4, 0>, fg, fb, 0, f); break;
-        case 1: launch_timed(h, GNN_K_FWD_GEMM0, fwd_first_kernel<4, 1>, fg, fb, 0, f); break;
-        case 2: launch_timed(h, GNN_K_FWD_GEMM0, fwd_first_kernel<4, 2>, fg, fb, 0, f); break;
-        case 3: launch_timed(h, GNN_K_FWD_GEMM0, fwd_first_kernel<4, 3>, fg, fb, 0, f); break;
-        default: launch_timed(h, GNN_K_FWD_GEMM0, fwd_first_kernel<4, 4>, fg, fb, 0, f); break;
-        }
-    } else {
-        const dim3 fb(FIRST_NW * 64);
-        switch (h->inner_act) {
-        case 0: launch_timed(h, GNN_K_FWD_GEMM0, fwd_first_kernel<FIRST_NW, 0>, fg, fb, 0, f); break;
-        case 1: launch_timed(h, GNN_K_FWD_GEMM0, fwd_first_kernel<FIRST_NW, 1>, fg, fb, 0, f); break;
-        case 2: launch_timed(h, GNN_K_FWD_GEMM0, fwd_first_kernel<FIRST_NW, 2>, fg, fb, 0, f); break;
-        case 3: launch_timed(h, GNN_K_FWD_GEMM0, fwd_first_kernel<FIRST_NW, 3>, fg, fb, 0, f); break;
-        default: launch_timed(h, GNN_K_FWD_GEMM0, fwd_first_kernel<FIRST_NW, 4>, fg, fb, 0, f); break;
-        }
-    }
+    with_act(h->inner_act, [&](auto A) {
+        constexpr int a = decltype(A)::value;
+        if (f.K / 16 <= 4 * 13) launch_timed(h, GNN_K_FWD_GEMM0, fwd_first_kernel<4, a>, fg, dim3(4 * 64), 0, f);
+        else launch_timed(h, GNN_K_FWD_GEMM0, fwd_first_kernel<FIRST_NW, a>, fg, dim3(FIRST_NW * 64), 0, f);
+    });
 }
 
 void fused_gradient(gnn_mlp *h, const float *a0, int B, bool fused_update, float step_over_b, float momentum) {

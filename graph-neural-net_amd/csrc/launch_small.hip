@@ -1,5 +1,6 @@
-// launch_small.hip -- host side of the small-net path: the row-block kernel (middle4_kernel.h, with its run-time
-// instantiation, jit.h) and the tile-owner kernel (tile_step_kernel.h).
+// launch_small.hip -- host side of the small-net path: the row-block kernels (middle4_kernel.h, rowblock_kernel.h, with their
+// run-time instantiation, jit.h) and the tile-owner kernel (tile_step_kernel.h).  Which instance runs: the table of
+// instances.h / static_shapes.h, asked here for the single-net families; every launch goes through launch_instance (handle.h).
 #include "static_shapes.h"
 #include "jit.h"
 
@@ -27,44 +28,46 @@ int static_shape_of(const gnn_mlp *h) {
 }
 
 const void *mid4_function(const gnn_mlp *h, int variant) {
+    const bool softmax = h->out_kind == GNN_OUT_SOFTMAX_CE;
     const int which = static_shape_of(h);
-    if (which >= 0)
-        return h->out_kind == GNN_OUT_SOFTMAX_CE ? mid4_static_table<0>(which, h->inner_act, variant) : mid4_static_general(which, h->inner_act, variant);
-    // runtime extents: layer count templated (3..6, else generic), activation read from the arguments
-#define GNN_M4RO(NL, OK) (variant == 3 ? reinterpret_cast<const void *>(&middle4_kernel<RuntimeShape<NL>, -1, OK, true, true, true>) \
-                          : variant == 2 ? reinterpret_cast<const void *>(&middle4_kernel<RuntimeShape<NL>, -1, OK, true, true>) \
-                          : variant == 1 ? reinterpret_cast<const void *>(&middle4_kernel<RuntimeShape<NL>, -1, OK, true>)           \
-                                         : reinterpret_cast<const void *>(&middle4_kernel<RuntimeShape<NL>, -1, OK, false>))
-#define GNN_M4R(NL) (h->out_kind == GNN_OUT_SOFTMAX_CE ? GNN_M4RO(NL, 0) : GNN_M4RO(NL, 1))
-    switch (h->L) {
-    case 3: return GNN_M4R(3);
-    case 4: return GNN_M4R(4);
-    case 5: return GNN_M4R(5);
-    case 6: return GNN_M4R(6);
-    default: return GNN_M4R(0);
+    if (which >= 0) return softmax ? mid4_static_table<0>(which, h->inner_act, variant) : mid4_static_general(which, h->inner_act, variant);
+    return softmax ? mid4_runtime_instance<0>(h->L, variant) : mid4_runtime_instance<1>(h->L, variant);
+}
+
+// What both row kernels' parameter structs (Mid4Params, RbParams: kernel ABI, same field names) take from the handle.
+// At plan time: the middle weights, activations and deltas.
+template <class P> void bind_net(const gnn_mlp *h, P &p) {
+    const int Lm = h->L - 1;
+    for (int l = 1; l < Lm; l++) { p.W[l] = h->W + h->w_off[l]; p.act[l] = h->act[l]; }
+    for (int l = 1; l <= Lm; l++) p.delta[l] = h->delta[l];
+    if (h->dtype == GNN_DTYPE_BF16) {
+        for (int l = 1; l < Lm; l++) { p.Wb[l] = h->Wb + h->w_off[l]; p.actb[l] = h->actb[l]; }
+        for (int l = 1; l <= Lm; l++) p.deltab[l] = h->deltab[l];
     }
-#undef GNN_M4R
-#undef GNN_M4RO
+    p.last_act = h->last_act;
+    p.inner_act = h->inner_act;
+}
+// Per call: the slabs, the batch's expected rows and what the caller wants back.
+template <class P> void bind_call(const gnn_mlp *h, P &p, const float *y, int B, bool want_prob, bool want_loss, bool want_label) {
+    p.slabs = h->slabs; p.slab_rows = h->cap_rows;
+    p.Y = y; p.ldy = h->ld[h->L - 1];
+    p.prob = want_prob ? h->prob : nullptr;
+    p.loss = want_loss ? h->lossv : nullptr;
+    p.label = want_label ? h->labels : nullptr;
+    p.B = B;
+    p.row_idx = h->cur_idx;
 }
 
 void plan_mid4(gnn_mlp *h) {
     h->mid4 = false;
     if (h->env_path == 2) { h->plan_note = "row-block kernel switched off (GNN_MLP_PATH=nomid4)"; return; } // tests: force the per-layer middle
-    const int L = h->L, Lm = L - 1;
     Mid4Params &m = h->mid4p;
     m = Mid4Params{};
     const bool bf16 = h->dtype == GNN_DTYPE_BF16;
-    m.plan = make_mid4_plan(h->dims.data(), L, bf16);
+    m.plan = make_mid4_plan(h->dims.data(), h->L, bf16);
     if (!m.plan.ok) return; // (plan_fused notes that the middle weights do not fit LDS)
     h->mid4_lds_bytes = (size_t)m.plan.lds_floats * sizeof(float);
-    for (int l = 1; l < Lm; l++) { m.W[l] = h->W + h->w_off[l]; m.act[l] = h->act[l]; }
-    for (int l = 1; l <= Lm; l++) m.delta[l] = h->delta[l];
-    if (bf16) {
-        for (int l = 1; l < Lm; l++) { m.Wb[l] = h->Wb + h->w_off[l]; m.actb[l] = h->actb[l]; }
-        for (int l = 1; l <= Lm; l++) m.deltab[l] = h->deltab[l];
-    }
-    m.last_act = h->last_act;
-    m.inner_act = h->inner_act;
+    bind_net(h, m);
     h->specialization = static_shape_of(h) >= 0 ? 1 : 0;
     for (int bwd = (bf16 ? 2 : 0); bwd < 3; bwd++) {
         h->mid4_fn[bwd] = mid4_function(h, (bf16 && bwd == 2) ? 3 : bwd);
@@ -78,11 +81,6 @@ void plan_mid4(gnn_mlp *h) {
 }
 
 // ---- rowblock_kernel plan -----------------------------------------------------------------------
-template <int NL, bool BF> const void *rb_fn_runtime(int out_kind) {
-    return out_kind == GNN_OUT_SOFTMAX_CE ? reinterpret_cast<const void *>(&rowblock_kernel<RbRuntimeShape<NL>, -1, 0, BF>)
-                                          : reinterpret_cast<const void *>(&rowblock_kernel<RbRuntimeShape<NL>, -1, 1, BF>);
-}
-
 void plan_rowblock(gnn_mlp *h) {
     h->rb = false;
     h->rb_fn = nullptr; h->rb_jit = nullptr; h->rb_static = 0;
@@ -93,32 +91,16 @@ void plan_rowblock(gnn_mlp *h) {
     r = RbParams{};
     r.plan = make_rb_plan(h->dims.data(), h->L);
     if (!r.plan.ok) return; // (the two-launch step then keeps middle4_kernel as its row-block kernel)
-    const int L = h->L, Lm = L - 1;
     h->rb_lds_bytes = (size_t)r.plan.lds_floats * sizeof(float);
-    for (int l = 1; l < Lm; l++) { r.W[l] = h->W + h->w_off[l]; r.act[l] = h->act[l]; }
-    for (int l = 1; l <= Lm; l++) r.delta[l] = h->delta[l];
-    if (bf) {
-        for (int l = 1; l < Lm; l++) { r.Wb[l] = h->Wb + h->w_off[l]; r.actb[l] = h->actb[l]; }
-        for (int l = 1; l <= Lm; l++) r.deltab[l] = h->deltab[l];
-    }
-    r.last_act = h->last_act;
-    r.inner_act = h->inner_act;
+    bind_net(h, r);
     r.slabs = h->slabs; r.slab_rows = h->cap_rows;
+    const bool softmax = h->out_kind == GNN_OUT_SOFTMAX_CE;
     const int which = static_shape_of(h);
     if (which >= 0) {
-        h->rb_fn = h->out_kind == GNN_OUT_SOFTMAX_CE ? rb_static_table<0>(which, h->inner_act, bf) : rb_static_general(which, h->inner_act, bf);
+        h->rb_fn = softmax ? rb_static_table<RbSingle, 0>(which, h->inner_act, bf) : rb_static_general(which, h->inner_act, bf);
         h->rb_static = 1;
     }
-    else if (bf) h->rb_fn = L == 3 ? rb_fn_runtime<3, true>(h->out_kind) : rb_fn_runtime<4, true>(h->out_kind);
-    else {
-        switch (L) {
-        case 3: h->rb_fn = rb_fn_runtime<3, false>(h->out_kind); break;
-        case 4: h->rb_fn = rb_fn_runtime<4, false>(h->out_kind); break;
-        case 5: h->rb_fn = rb_fn_runtime<5, false>(h->out_kind); break;
-        case 6: h->rb_fn = rb_fn_runtime<6, false>(h->out_kind); break;
-        default: h->rb_fn = rb_fn_runtime<0, false>(h->out_kind); break;
-        }
-    }
+    else h->rb_fn = softmax ? rb_runtime_instance<RbSingle, 0>(h->L, bf) : rb_runtime_instance<RbSingle, 1>(h->L, bf);
     if (hipFuncSetAttribute(h->rb_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->rb_lds_bytes) != hipSuccess) {
         (void)hipGetLastError();
         h->rb_fn = nullptr;
@@ -154,13 +136,7 @@ void fused_forward(gnn_mlp *h, const float *a0, const float *y, int B, bool back
     if (!from_slabs) launch_fwd_first(h, a0, B);
     if (from_slabs && h->rb) { // the two-launch step's training kernel (rowblock_kernel.h)
         RbParams r = h->rbp;
-        r.slabs = h->slabs; r.slab_rows = h->cap_rows;
-        r.Y = y; r.ldy = h->ld[h->L - 1];
-        r.prob = want_prob ? h->prob : nullptr;
-        r.loss = want_loss ? h->lossv : nullptr;
-        r.label = want_label ? h->labels : nullptr;
-        r.B = B;
-        r.row_idx = h->cur_idx;
+        bind_call(h, r, y, B, want_prob, want_loss, want_label);
         if (copy_rows == RB_COPY_CURRENT && h->cur_idx) { // the sampled batch's rows, contiguous, for the tile kernel that follows (RbParams::xcopy)
             r.ldx = h->ld[0]; r.copy_idx = h->cur_idx;
             if (h->dtype == GNN_DTYPE_BF16) { r.Xb = a0_bf16(h, a0); r.xcopyb = h->xstage_b[h->la.xstage_cur]; }
@@ -177,61 +153,30 @@ void fused_forward(gnn_mlp *h, const float *a0, const float *y, int B, bool back
         void *args[] = {&r.slabs, &hd_W1, &hd_Wl, &r.row_idx, &r.Y, &r.copy_idx, &r.B, &r.slab_rows, &r.ldy, &r};
         const unsigned grid = (unsigned)(pad_up(B) / 4);
         if (h->grp) { launch_rowblock_group(h, grid, args); return; } // every member of a group (group_kernels.hip)
-        TimerClass &tc = h->timers[GNN_K_MIDDLE];
-        hipEvent_t ev0 = nullptr, ev1 = nullptr;
-        if (h->timing && tc.used < 8192) {
-            if (tc.used >= tc.start.size()) {
-                hipEvent_t a = nullptr, b = nullptr;
-                if (hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess) { tc.start.push_back(a); tc.stop.push_back(b); }
-            }
-            if (tc.used < tc.start.size()) { ev0 = tc.start[tc.used]; ev1 = tc.stop[tc.used]; tc.used++; }
-        }
-        hipError_t le;
-        if (h->rb_jit) le = hipExtModuleLaunchKernel(h->rb_jit, grid * (unsigned)RB_NT, 1, 1, RB_NT, 1, 1, h->rb_lds_bytes, h->stream, args, nullptr, ev0, ev1, 0);
-        else if (ev0) le = hipExtLaunchKernel(const_cast<void *>(h->rb_fn), dim3(grid), dim3(RB_NT), args, h->rb_lds_bytes, h->stream, ev0, ev1, 0);
-        else le = hipLaunchKernel(h->rb_fn, dim3(grid), dim3(RB_NT), args, h->rb_lds_bytes, h->stream);
-        if (le != hipSuccess && h->launch_error == hipSuccess) h->launch_error = le;
+        launch_instance(h, GNN_K_MIDDLE, h->rb_fn, h->rb_jit, dim3(grid), dim3(RB_NT), h->rb_lds_bytes, args);
         return;
     }
-    {
-        Mid4Params m4 = h->mid4p;
-        for (int l = 1; l < h->L - 1; l++) m4.act[l] = h->act[l]; // (the evaluation workspace may stand in: plan.hip, EvalScope)
-        m4.slabs = h->slabs; m4.slab_rows = h->cap_rows; m4.n_slabs = h->n_slabs;
-        m4.Y = y; m4.ldy = h->ld[h->L - 1];
-        m4.prob = want_prob ? h->prob : nullptr;
-        m4.loss = want_loss ? h->lossv : nullptr;
-        m4.label = want_label ? h->labels : nullptr;
-        m4.B = B;
-        m4.row_idx = h->cur_idx;
-        void *args[] = {&m4};
-        // every padded row is processed: rows >= B become zeros
-        const int bw = from_slabs ? 2 : backward ? 1 : 0;
-        const unsigned grid = (unsigned)(pad_up(B) / 4);
-        TimerClass &tc = h->timers[GNN_K_MIDDLE];
-        hipEvent_t ev0 = nullptr, ev1 = nullptr;
-        if (h->timing && tc.used < 8192) {
-            if (tc.used >= tc.start.size()) {
-                hipEvent_t a = nullptr, b = nullptr;
-                if (hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess) { tc.start.push_back(a); tc.stop.push_back(b); }
-            }
-            if (tc.used < tc.start.size()) { ev0 = tc.start[tc.used]; ev1 = tc.stop[tc.used]; tc.used++; }
-        }
-        hipError_t le;
-        if (h->mid4_jit[bw]) { // module function: global size is given in threads
-            le = hipExtModuleLaunchKernel(h->mid4_jit[bw], grid * 1024u, 1, 1, 1024, 1, 1, h->mid4_lds_bytes, h->stream, args,
-                                          nullptr, ev0, ev1, 0);
-        } else if (ev0) {
-            le = hipExtLaunchKernel(const_cast<void *>(h->mid4_fn[bw]), dim3(grid), dim3(1024), args, h->mid4_lds_bytes,
-                                    h->stream, ev0, ev1, 0);
-        } else {
-            le = hipLaunchKernel(h->mid4_fn[bw], dim3(grid), dim3(1024), args, h->mid4_lds_bytes, h->stream);
-        }
-        // a refused launch must not pass for a step: callers read it back through hipGetLastError / launch_error
-        if (le != hipSuccess && h->launch_error == hipSuccess) h->launch_error = le;
-    }
+    Mid4Params m4 = h->mid4p;
+    for (int l = 1; l < h->L - 1; l++) m4.act[l] = h->act[l]; // (the evaluation workspace may stand in: plan.hip, EvalScope)
+    bind_call(h, m4, y, B, want_prob, want_loss, want_label);
+    m4.n_slabs = h->n_slabs;
+    void *args[] = {&m4};
+    const int bw = from_slabs ? 2 : backward ? 1 : 0;
+    // every padded row is processed: rows >= B become zeros
+    launch_instance(h, GNN_K_MIDDLE, h->mid4_fn[bw], h->mid4_jit[bw], dim3((unsigned)(pad_up(B) / 4)), dim3(1024), h->mid4_lds_bytes, args);
 }
 
 // ---- tile_step_kernel launches ------------------------------------------------------------------
+// the single-net families of tile_step_instance (instances.h), peer forms included
+struct TileF32 {
+    static constexpr bool kPeerForms = true;
+    template <int S, int D, bool F> static const void *fn() { return GNN_KERNEL(tile_step_kernel<S, D, F>); }
+};
+struct TileBf16 {
+    static constexpr bool kPeerForms = true;
+    template <int S, int D, bool F> static const void *fn() { return GNN_KERNEL(tile_step_bf16_kernel<S, D, F>); }
+};
+
 // gsrc / gdst / fwd as in tile_step_kernel.h; fwd_only_layer0: the grid covers layer 0's tiles only
 // staged: the current batch's rows come from the contiguous copy xstage[xstage_cur] instead of (a0, cur_idx)
 void launch_tile_step(gnn_mlp *h, int gsrc, int gdst, const NextBatch *next, const float *a0, int B, float step_over_b, float momentum,
@@ -264,29 +209,9 @@ void launch_tile_step(gnn_mlp *h, int gsrc, int gdst, const NextBatch *next, con
         if (fwd) t.Anb = next_staged ? h->xstage_b[stage_dst] : a0_bf16(h, next->a0);
     }
     if (h->grp) { launch_tile_step_group(h, gsrc, gdst, fwd, grid.x, t, B); return; } // every member of a group (group_kernels.hip)
-    if (h->dtype == GNN_DTYPE_BF16) {
-        if (fwd_only) launch_timed(h, cls, tile_step_bf16_kernel<0, 0, true>, grid, block, 0, t);
-        else if (gsrc == 1 && gdst == 1) launch_timed(h, cls, tile_step_bf16_kernel<1, 1, false>, grid, block, 0, t);
-        else if (gsrc == 1 && gdst == 2 && !fwd) launch_timed(h, cls, tile_step_bf16_kernel<1, 2, false>, grid, block, 0, t);
-        else if (gsrc == 1 && gdst == 2 && fwd) launch_timed(h, cls, tile_step_bf16_kernel<1, 2, true>, grid, block, 0, t);
-        else if (gsrc == 2 && gdst == 2 && !fwd) launch_timed(h, cls, tile_step_bf16_kernel<2, 2, false>, grid, block, 0, t);
-        else if (gsrc == 2) launch_timed(h, cls, tile_step_bf16_kernel<2, 2, true>, grid, block, 0, t);
-        else if (gsrc == 3 && !fwd) launch_timed(h, cls, tile_step_bf16_kernel<3, 2, false>, grid, block, 0, t);
-        else if (gsrc == 3) launch_timed(h, cls, tile_step_bf16_kernel<3, 2, true>, grid, block, 0, t);
-        else if (!fwd) launch_timed(h, cls, tile_step_bf16_kernel<4, 2, false>, grid, block, 0, t);
-        else launch_timed(h, cls, tile_step_bf16_kernel<4, 2, true>, grid, block, 0, t);
-        return;
-    }
-    if (fwd_only) launch_timed(h, cls, tile_step_kernel<0, 0, true>, grid, block, 0, t);
-    else if (gsrc == 1 && gdst == 1) launch_timed(h, cls, tile_step_kernel<1, 1, false>, grid, block, 0, t);
-    else if (gsrc == 1 && gdst == 2 && !fwd) launch_timed(h, cls, tile_step_kernel<1, 2, false>, grid, block, 0, t);
-    else if (gsrc == 1 && gdst == 2 && fwd) launch_timed(h, cls, tile_step_kernel<1, 2, true>, grid, block, 0, t);
-    else if (gsrc == 2 && gdst == 2 && !fwd) launch_timed(h, cls, tile_step_kernel<2, 2, false>, grid, block, 0, t);
-    else if (gsrc == 2) launch_timed(h, cls, tile_step_kernel<2, 2, true>, grid, block, 0, t);
-    else if (gsrc == 3 && !fwd) launch_timed(h, cls, tile_step_kernel<3, 2, false>, grid, block, 0, t);
-    else if (gsrc == 3) launch_timed(h, cls, tile_step_kernel<3, 2, true>, grid, block, 0, t);
-    else if (!fwd) launch_timed(h, cls, tile_step_kernel<4, 2, false>, grid, block, 0, t);
-    else launch_timed(h, cls, tile_step_kernel<4, 2, true>, grid, block, 0, t);
+    const void *fn = h->dtype == GNN_DTYPE_BF16 ? tile_step_instance<TileBf16>(gsrc, gdst, fwd) : tile_step_instance<TileF32>(gsrc, gdst, fwd);
+    void *args[] = {&t};
+    launch_instance(h, cls, fn, nullptr, grid, block, 0, args);
 }
 
 } // namespace host
