@@ -10,6 +10,7 @@
 // through their own handles: the same results, no speed-up.
 #include "handle.h"
 
+#include <algorithm>
 #include <memory>
 
 using namespace gnn;
@@ -222,6 +223,78 @@ int gnn_mlp_group_train_sampled(gnn_mlp_group_t *g, gnn_sampler_t *s, int iterat
     }
     leave_grouped(g, h0->time - t0);
     return rc;
+}); }
+
+/* The observed loop (NNT:68-72 / 75-79) of a group: the sampled loop above with, behind every step and still under the
+ * GroupScope, ONE launch of the forward kernel's validation form per block of validation rows (group_eval.hip) -- the members'
+ * per-row losses of iteration i go to row i mod M of a matrix [M][K][stride], which ONE launch of group_curve_sum_kernel turns
+ * into d_val[i][k] whenever it is full and behind the last step.  Everything is allocated and checked before the first step. */
+namespace {
+constexpr int kCurveRows = 256;
+struct GroupValidation : SampledObserver {
+    gnn_mlp_group *g; int validation_size, iterations, M; int64_t stride;
+    float *d_rows; double *d_val;
+    int summed = 0; // iterations whose rows are summed already (or whose sum is enqueued)
+    int sum_through(int i_end) {
+        if (i_end == summed) return GNN_OK;
+        TRY(enqueue_group_curve_sum(g, d_rows, i_end - summed, stride, validation_size, d_val + (size_t)summed * g->K)); // (summed is a multiple of M: matrix rows 0 ..)
+        summed = i_end;
+        return GNN_OK;
+    }
+    int after_step(int i) override {
+        TRY(enqueue_group_validation(g, validation_size, d_rows + (size_t)(i % M) * g->K * stride, stride));
+        return (i + 1) % M == 0 ? sum_through(i + 1) : GNN_OK;
+    }
+    int after_chunk(int i_end) override {
+        TRY_LAUNCHES(g->m[0]);
+        return i_end == iterations ? sum_through(i_end) : GNN_OK; // (in front of the loop's own wait for the stream)
+    }
+};
+} // namespace
+
+int gnn_mlp_group_observed_launches(const gnn_mlp_group_t *g) { return !g ? -1 : (g->grouped && g->K > 1 && g->eval_plan.ok) ? 3 : 0; }
+
+int gnn_mlp_group_train_sampled_observed(gnn_mlp_group_t *g, gnn_sampler_t *s, int iterations, int batch, const double *steps,
+                                         const double *momenta, int noise, int validation_size, double *val_loss) { return guarded([&]() -> int {
+    TRY(check_group(g));
+    TRY(check_per_member(g, steps, momenta));
+    gnn_mlp *h0 = g->m[0];
+    TRY(train_sampled_checks(h0, s, iterations, batch, steps[0], noise));
+    if (!val_loss) return fail(GNN_ERR_BAD_ARG, "null output");
+    if (validation_size <= 0 || validation_size > h0->dataset_n) return fail(GNN_ERR_BAD_ARG, "validation size outside the dataset (NNT:104)");
+    const int K = g->K;
+    if (gnn_mlp_group_observed_launches(g) != 3) { // member after member, the sampler rewound for each: column k is the lone handle's curve
+        std::unique_ptr<gnn_sampler_t, int (*)(gnn_sampler_t *)> start(sampler_copy(s), gnn_sampler_destroy);
+        std::vector<double> col((size_t)iterations);
+        for (int k = 0; k < K; k++) {
+            if (k) sampler_assign(s, start.get());
+            TRY(gnn_mlp_train_sampled_observed(g->m[(size_t)k], s, iterations, batch, steps[k], momenta[k], noise, validation_size, col.data()));
+            for (int i = 0; i < iterations; i++) val_loss[(size_t)i * K + k] = col[(size_t)i];
+        }
+        return GNN_OK;
+    }
+    GroupValidation obs;
+    obs.g = g; obs.validation_size = validation_size; obs.iterations = iterations;
+    obs.M = std::min(iterations, kCurveRows); obs.stride = pad_up(validation_size);
+    DevScratch rows, val;
+    TRY(rows.alloc(sizeof(float) * (size_t)obs.M * K * (size_t)obs.stride));
+    TRY(val.alloc(sizeof(double) * (size_t)iterations * K));
+    obs.d_rows = rows.as<float>(); obs.d_val = val.as<double>();
+    TRY(enter_grouped(g));
+    GroupLaunch gl;
+    TRY(group_launch(g, steps, momenta, &gl));
+    const int t0 = h0->time;
+    int rc;
+    {
+        GroupScope scope(h0, &gl);
+        rc = train_sampled_run(h0, s, iterations, batch, steps[0], momenta[0], noise, &obs);
+    }
+    leave_grouped(g, h0->time - t0);
+    TRY(rc);
+    // (the loop has waited for the stream behind the last sum: one readback)
+    HIP_TRY(hipMemcpy(val_loss, val.p, sizeof(double) * (size_t)iterations * K, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < (size_t)iterations * K; i++) val_loss[i] /= (double)validation_size; // NNT:112
+    return GNN_OK;
 }); }
 
 } // extern "C"

@@ -6,6 +6,9 @@
 // the members run one after another, each its own do_forward under its EvalScope in blocks of its own eval_block_rows, and
 // the same combine kernel reads the members' own prob / lossv / labels buffers: the same results up to near-ties, no speed-up.
 // Evaluation writes no weight, no momentum, no step count and no look-ahead state.
+//
+// The validation pass of a group's observed training loop (group.hip: gnn_mlp_group_train_sampled_observed) is enqueued from
+// here too: the forward kernel's LOSS_ONLY form into a row of the curve matrix, and group_curve_sum_kernel over that matrix.
 #include "handle.h"
 
 #include <algorithm>
@@ -29,8 +32,12 @@ constexpr int kGroupedMaxBlockRowsF32 = 10000;
 // rows of at most 1024 padded inputs, hidden layers of at most 1024, and the two activation images + the weight / row chunks
 // within 160 KiB of LDS -- with tiles of 32 rows if that fits, else of 16.  Every net of the two-launch training path passes.
 struct GroupEvalPlan {
-    bool ok = false; int mt = 0; GroupEvalLds lds{}; const void *fn = nullptr;
+    bool ok = false; int mt = 0; GroupEvalLds lds{}; const void *fn = nullptr, *fn_loss = nullptr;
 };
+template <bool LOSS_ONLY> const void *forward_instance(bool bf, int mt) {
+    return bf ? (mt == 2 ? reinterpret_cast<const void *>(group_forward_kernel<2, true, LOSS_ONLY>) : reinterpret_cast<const void *>(group_forward_kernel<1, true, LOSS_ONLY>))
+              : (mt == 2 ? reinterpret_cast<const void *>(group_forward_kernel<2, false, LOSS_ONLY>) : reinterpret_cast<const void *>(group_forward_kernel<1, false, LOSS_ONLY>));
+}
 GroupEvalPlan make_plan(const gnn_mlp *h) {
     GroupEvalPlan pl;
     const bool bf = h->dtype == GNN_DTYPE_BF16;
@@ -38,8 +45,8 @@ GroupEvalPlan make_plan(const gnn_mlp *h) {
         const GroupEvalLds m = ge_lds(h->ld.data(), h->L, bf, mt);
         if (!m.ok) continue;
         pl.ok = true; pl.mt = mt; pl.lds = m;
-        pl.fn = bf ? (mt == 2 ? reinterpret_cast<const void *>(group_forward_kernel<2, true>) : reinterpret_cast<const void *>(group_forward_kernel<1, true>))
-                   : (mt == 2 ? reinterpret_cast<const void *>(group_forward_kernel<2, false>) : reinterpret_cast<const void *>(group_forward_kernel<1, false>));
+        pl.fn = forward_instance<false>(bf, mt);
+        pl.fn_loss = forward_instance<true>(bf, mt);
     }
     return pl;
 }
@@ -55,6 +62,26 @@ int ensure_workspace(gnn_mlp_group *g, int rows) {
     HIP_TRY(hipMalloc(reinterpret_cast<void **>(&g->eval_ws), sizeof(float) * (size_t)g->K * want * 18));
     g->eval_ws_rows = want;
     return GNN_OK;
+}
+
+// what both forms of the forward kernel take: the block's rows [first, first + B) of the data set, the net, the LDS plan
+GroupEvalParams forward_params(const gnn_mlp_group *g, int64_t first, int B) {
+    const gnn_mlp *h0 = g->m[0];
+    const int Lm = h0->L - 1;
+    const bool bf = h0->dtype == GNN_DTYPE_BF16;
+    GroupEvalParams p{};
+    p.X = bf ? static_cast<const void *>(h0->DXb + (size_t)first * h0->ld[0]) : static_cast<const void *>(h0->DX + (size_t)first * h0->ld[0]);
+    p.Y = h0->DY + (size_t)first * h0->ld[Lm]; p.ldy = h0->ld[Lm];
+    p.W = bf ? static_cast<const void *>(h0->Wb) : static_cast<const void *>(h0->W);
+    p.S = g->S;
+    p.rows = B; p.L = h0->L;
+    for (int l = 0; l < h0->L; l++) { p.d[l] = h0->dims[l]; p.ld[l] = h0->ld[l]; }
+    for (int l = 0; l < Lm; l++) p.w_off[l] = (unsigned)h0->w_off[l];
+    p.inner_act = h0->inner_act; p.last_act = h0->last_act; p.out_kind = h0->out_kind;
+    const GroupEvalLds &m = g->eval_plan.lds;
+    p.off_img[0] = m.off_img[0]; p.off_img[1] = m.off_img[1]; p.ldi[0] = m.ldi[0]; p.ldi[1] = m.ldi[1];
+    p.off_w = m.off_w; p.off_x = m.off_x; p.off_z = m.off_z;
+    return p;
 }
 
 struct EvalOut { // device results of one call
@@ -88,22 +115,11 @@ int run_blocks(gnn_mlp_group *g, int64_t first, int64_t n, const EvalOut &o) {
         const float *y = h0->DY + (size_t)(first + off) * ldo;
         if (grouped) {
             const size_t cap_rows = (size_t)g->eval_ws_rows;
-            GroupEvalParams p{};
-            p.X = bf ? static_cast<const void *>(h0->DXb + (size_t)(first + off) * h0->ld[0])
-                     : static_cast<const void *>(h0->DX + (size_t)(first + off) * h0->ld[0]);
-            p.Y = y; p.ldy = ldo;
-            p.W = bf ? static_cast<const void *>(h0->Wb) : static_cast<const void *>(h0->W);
-            p.S = g->S;
+            GroupEvalParams p = forward_params(g, first + off, B);
             p.out = g->eval_ws; p.loss = g->eval_ws + cap_rows * 16;
             p.label = reinterpret_cast<int32_t *>(g->eval_ws + cap_rows * 17);
             p.ws_stride = cap_rows * 18;
-            p.rows = B; p.L = h0->L;
-            for (int l = 0; l < h0->L; l++) { p.d[l] = h0->dims[l]; p.ld[l] = h0->ld[l]; }
-            for (int l = 0; l < Lm; l++) p.w_off[l] = (unsigned)h0->w_off[l];
-            p.inner_act = h0->inner_act; p.last_act = h0->last_act; p.out_kind = h0->out_kind;
             const GroupEvalLds &m = g->eval_plan.lds;
-            p.off_img[0] = m.off_img[0]; p.off_img[1] = m.off_img[1]; p.ldi[0] = m.ldi[0]; p.ldi[1] = m.ldi[1];
-            p.off_w = m.off_w; p.off_x = m.off_x; p.off_z = m.off_z;
             const int R = 16 * g->eval_plan.mt;
             void *args[] = {&p};
             HIP_TRY(hipLaunchKernel(g->eval_plan.fn, dim3((unsigned)((B + R - 1) / R), (unsigned)g->K), dim3(GE_NT), args,
@@ -160,11 +176,38 @@ void plan_group_eval(gnn_mlp_group *g) {
     const GroupEvalPlan pl = make_plan(g->m[0]);
     g->eval_plan.ok = false;
     if (!pl.ok) return;
-    if (hipFuncSetAttribute(pl.fn, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds.bytes) != hipSuccess) {
+    if (hipFuncSetAttribute(pl.fn, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds.bytes) != hipSuccess ||
+        hipFuncSetAttribute(pl.fn_loss, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds.bytes) != hipSuccess) {
         (void)hipGetLastError();
         return;
     }
-    g->eval_plan.ok = true; g->eval_plan.mt = pl.mt; g->eval_plan.lds = pl.lds; g->eval_plan.fn = pl.fn;
+    g->eval_plan.ok = true; g->eval_plan.mt = pl.mt; g->eval_plan.lds = pl.lds; g->eval_plan.fn = pl.fn; g->eval_plan.fn_loss = pl.fn_loss;
+}
+
+// Always the grouped form, whatever n: a block is the evaluation block of run_blocks, for f32 nets capped where run_blocks
+// leaves the grouped form -- a row's loss does not depend on the block it is in.  Never do_forward: member 0 launches for the
+// group while the training loop runs (GroupLaunch), and its own forward path would become grouped launches.
+int enqueue_group_validation(gnn_mlp_group *g, int n, float *loss_rows, int64_t stride) {
+    const gnn_mlp *h0 = g->m[0];
+    int block = block_cap(h0);
+    if (h0->dtype != GNN_DTYPE_BF16) block = std::min(block, kGroupedMaxBlockRowsF32);
+    const int R = 16 * g->eval_plan.mt;
+    for (int off = 0; off < n; off += block) {
+        const int B = std::min(block, n - off);
+        GroupEvalParams p = forward_params(g, off, B);
+        p.loss = loss_rows + off; p.loss_stride = (unsigned)stride;
+        void *args[] = {&p};
+        HIP_TRY(hipLaunchKernel(g->eval_plan.fn_loss, dim3((unsigned)((B + R - 1) / R), (unsigned)g->K), dim3(GE_NT), args,
+                                (size_t)g->eval_plan.lds.bytes, h0->stream));
+    }
+    return GNN_OK;
+}
+
+int enqueue_group_curve_sum(gnn_mlp_group *g, const float *rows, int n_rows, int64_t stride, int n, double *d_out) {
+    hipLaunchKernelGGL(group_curve_sum_kernel, dim3((unsigned)n_rows, (unsigned)g->K), dim3(256), 0, g->m[0]->stream,
+                       CurveSumParams{rows, (unsigned long long)stride, n, d_out});
+    HIP_TRY(hipGetLastError());
+    return GNN_OK;
 }
 
 void free_group_eval(gnn_mlp_group *g) {

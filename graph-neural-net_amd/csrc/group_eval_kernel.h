@@ -6,6 +6,8 @@
 //                          into fp64 partial sums with one fixed order, the ensemble's mean output (s = out_0; s += out_k in
 //                          member order, one division by (float)K) and the reference's argmax of that mean row;
 //   group_loss_finish_kernel  adds the workgroups' loss slots in index order.
+//   group_curve_sum_kernel    the curve matrix of a group's observed training loop (rows written by the forward kernel's
+//                          LOSS_ONLY form) summed row by row in fp64.
 //
 // The forward kernel.  Layer l+1 = f(A_l . W_l) is a K loop in chunks of KC rows of W_l: a chunk of the member's W_l (and,
 // for layer 0, the same K range of the tile's data-set rows) is brought to LDS with 16-B loads -- the next chunk's loads are
@@ -21,6 +23,7 @@
 #include "gemm_bf16.h"
 #include "fused_kernels.h"
 #ifndef __HIPCC_RTC__
+#include <cstddef>
 #include <type_traits>
 #endif
 
@@ -35,6 +38,8 @@ constexpr int GE_GROUP_MAX = 16; // (= GROUP_MAX of group_kernels.h)
 struct GroupEvalParams {
     const void *X;               // first row of the block: DX (f32) or DXb (bf16), leading dimension ld[0]
     const float *Y; int ldy;     // expected rows of the block
+    unsigned loss_stride;        // LOSS_ONLY: floats between members in `loss`, there a row [K][loss_stride] of the curve matrix (outside
+                                 // the arena).  In the four bytes that padded ldy: every other argument stays where it was.
     const void *W;               // member 0's W (f32) or Wb (bf16), the flat padded buffer
     unsigned long long S;        // bytes between members (the arena rule)
     float *out; float *loss; int32_t *label; // member 0's part of the workspace: [rows][16], [rows], [rows]
@@ -47,6 +52,8 @@ struct GroupEvalParams {
     // LDS (byte offsets; strides in elements): the two activation images, the weight chunk, the layer-0 row chunk, the last sums
     int off_img[2], ldi[2], off_w, off_x, off_z;
 };
+
+static_assert(offsetof(GroupEvalParams, loss_stride) == 20 && offsetof(GroupEvalParams, W) == 24, "loss_stride fills ldy's padding");
 
 // host + device: what the kernel needs in LDS for a net, and whether it applies at all (GroupEvalPlan, group_eval.hip)
 struct GroupEvalLds { int off_img[2], ldi[2], off_w, off_x, off_z, bytes; bool ok; };
@@ -84,7 +91,9 @@ __host__ __device__ constexpr GroupEvalLds ge_lds(const int *ld, int L, bool bf,
     return m;
 }
 
-template <int MT, bool BF>
+// LOSS_ONLY: the validation form (the observed training loop of a group, group_eval.hip) -- the same sums and, per row, the
+// same loss expressions, written to loss[member * loss_stride + row]; no output row, no label.
+template <int MT, bool BF, bool LOSS_ONLY = false>
 __global__ __launch_bounds__(GE_NT) void group_forward_kernel(GroupEvalParams p) {
     typedef typename std::conditional<BF, __bf16, float>::type T;
     typedef typename std::conditional<BF, bf16x8, float4>::type V16; // one 16-B piece
@@ -239,6 +248,40 @@ __global__ __launch_bounds__(GE_NT) void group_forward_kernel(GroupEvalParams p)
     __syncthreads();
 
     // the output rule, one thread per row (at most 16 outputs), from the unrounded f32 sums
+    if constexpr (LOSS_ONLY) {
+        if (t < R && row0 + t < p.rows) {
+            const int row = row0 + t, n = p.d[Lm];
+            const float *z = Zs + t * 17;
+            const float *y = p.Y + (size_t)row * p.ldy;
+            float mx = -__builtin_inff(), l = 0.f;
+            if (p.out_kind == 0) {
+#pragma unroll
+                for (int c = 0; c < 16; c++)
+                    if (c < n) {
+                        const float v = z[c];
+                        if (v >= mx) mx = v;
+                    }
+                float s = 0.f;
+#pragma unroll
+                for (int c = 0; c < 16; c++) s += c < n ? __expf(z[c] - mx) : 0.f;
+                const float lse = mx + __logf(s);
+#pragma unroll
+                for (int c = 0; c < 16; c++) {
+                    const float yy = c < n ? y[c] : 0.f;
+                    if (yy != 0.f) l += yy * (lse - z[c]); // -y ln p (SCE:213-217)
+                }
+            } else {
+#pragma unroll
+                for (int c = 0; c < 16; c++)
+                    if (c < n) {
+                        const float dd = act_fn(p.last_act, z[c]) - y[c];
+                        l += 0.5f * dd * dd; // GNN:236-239
+                    }
+            }
+            p.loss[member * (unsigned long long)p.loss_stride + row] = l;
+        }
+        return;
+    }
     if (t < R && row0 + t < p.rows) {
         const int row = row0 + t, n = p.d[Lm];
         const float *z = Zs + t * 17;
@@ -348,6 +391,28 @@ static __global__ __launch_bounds__(256) void group_combine_kernel(GroupCombineP
     }
     const unsigned long long m = __ballot(ens_hit);
     if ((t & 63) == 0 && m) atomicAdd(p.hits + p.K, (unsigned long long)__popcll(m));
+}
+
+// The curve matrix of a group's observed training loop summed: rows[(i * K + k) * stride + r] is the loss of validation row r
+// for member k after iteration i; workgroup (i, k) adds the row's `cols` LIVE entries (the pad behind them is never written and
+// never read) in fp64 -- a strided partial per thread, then one fixed tree: the same bits every time -- into out[i * K + k].
+struct CurveSumParams {
+    const float *rows; unsigned long long stride; int cols;
+    double *out;
+};
+static __global__ __launch_bounds__(256) void group_curve_sum_kernel(CurveSumParams p) {
+    __shared__ double part[256];
+    const size_t slot = (size_t)blockIdx.x * gridDim.y + blockIdx.y;
+    const float *r = p.rows + slot * p.stride;
+    double s = 0.0;
+    for (int i = threadIdx.x; i < p.cols; i += 256) s += (double)r[i];
+    part[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) p.out[slot] = part[0];
 }
 
 // member k's loss sum: the workgroups' slots in index order

@@ -188,7 +188,7 @@ struct gnn_mlp_group {
     const void *rb_fn = nullptr;  // the grouped row-block kernel (rb_group_function)
     // evaluation in grouped launches (group_eval_kernel.h): the plan made at create, and the workspace -- K x block rows x
     // (16 + 2) words, allocated on first use, grown on demand
-    struct EvalPlan { bool ok = false; int mt = 0; gnn::GroupEvalLds lds{}; const void *fn = nullptr; } eval_plan;
+    struct EvalPlan { bool ok = false; int mt = 0; gnn::GroupEvalLds lds{}; const void *fn = nullptr, *fn_loss = nullptr; } eval_plan; // (fn_loss: the LOSS_ONLY twin)
     float *eval_ws = nullptr;
     int eval_ws_rows = 0;
 };
@@ -199,6 +199,11 @@ namespace host {
 // ---- group_eval.hip ------------------------------------------------------------------------------
 void plan_group_eval(gnn_mlp_group *g); // at create: does group_forward_kernel apply to the group's net?
 void free_group_eval(gnn_mlp_group *g);
+// The validation pass of a group's observed training loop (needs eval_plan.ok; enqueues on member 0's stream, allocates nothing,
+// waits for nothing): every member's per-row losses of dataset rows [0, n) to loss_rows[k * stride + row] ...
+int enqueue_group_validation(gnn_mlp_group *g, int n, float *loss_rows, int64_t stride);
+// ... and n_rows x K such rows summed: d_out[i * K + k] = the fp64 sum of the first n entries of row (i, k)
+int enqueue_group_curve_sum(gnn_mlp_group *g, const float *rows, int n_rows, int64_t stride, int n, double *d_out);
 
 // ---- error convention (abi.hip) ---------------------------------------------------------------
 int fail(int code, const std::string &msg);   // records the calling thread's message, returns `code`
@@ -422,7 +427,16 @@ int upload_dataset_u8(gnn_mlp *h, const uint8_t *pixels, const uint8_t *labels, 
 int train_range_checks(gnn_mlp *h, int64_t first, int B, int n_steps, double step);
 int train_range_steps(gnn_mlp *h, int64_t first, int B, int s, int n_steps, double step, double momentum);
 int train_sampled_checks(gnn_mlp *h, gnn_sampler_t *s, int iterations, int batch, double step, int noise);
-int train_sampled_run(gnn_mlp *h, gnn_sampler_t *s, int iterations, int batch, double step, double momentum, int noise);
+// What the sampled training loop (sampler.hip: train_sampled_impl) calls between the steps it enqueues: after_step(i) when step
+// i's launches are on the handle's stream, after_chunk(i_end) when every step of a sampler chunk -- iterations up to i_end,
+// i_end == iterations for the last one -- is.  A status other than GNN_OK ends the loop.
+struct SampledObserver {
+    virtual int after_step(int i) = 0;
+    virtual int after_chunk(int i_end) { (void)i_end; return GNN_OK; }
+    virtual ~SampledObserver() {}
+};
+int train_sampled_run(gnn_mlp *h, gnn_sampler_t *s, int iterations, int batch, double step, double momentum, int noise,
+                      SampledObserver *obs = nullptr);
 gnn_sampler_t *sampler_copy(const gnn_sampler_t *s);
 void sampler_assign(gnn_sampler_t *dst, const gnn_sampler_t *src);
 

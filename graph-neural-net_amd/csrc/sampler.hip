@@ -136,8 +136,7 @@ bool validation_losses_to_row(gnn_mlp *h, int n, float *loss_row, int *rc) {
 } // namespace host
 } // namespace gnn
 
-// The loop NNT:60-92 on a resident dataset; d_val != null: the observed variants (NNT:68-72, 75-79) -- after iteration i the
-// summed validation loss of rows [0, validation_size) goes to d_val[i] (device).
+// The loop NNT:60-92 on a resident dataset.
 int gnn::host::train_sampled_checks(gnn_mlp *h, gnn_sampler_t *s, int iterations, int batch, double step, int noise) {
     if (!s) return fail(GNN_ERR_BAD_ARG, "null sampler");
     TRY(check_step_args(h, batch, step, noise));
@@ -151,8 +150,10 @@ int gnn::host::train_sampled_checks(gnn_mlp *h, gnn_sampler_t *s, int iterations
 gnn_sampler_t *gnn::host::sampler_copy(const gnn_sampler_t *s) { return new gnn_sampler(*s); }
 void gnn::host::sampler_assign(gnn_sampler_t *dst, const gnn_sampler_t *src) { *dst = *src; }
 
+// `obs` (handle.h: SampledObserver) is called behind every step and behind every sampler chunk, on the calling thread, with the
+// handle's stream holding everything enqueued so far: the observed loops below and the group's (group.hip) are this loop + one.
 static int train_sampled_impl(gnn_mlp_t *h, gnn_sampler_t *s, int iterations, int batch, double step, double momentum,
-                              int noise, int validation_size, double *d_val, float *d_rows = nullptr, int64_t row_stride = 0) {
+                              int noise, SampledObserver *obs) {
     TRY(check_handle(h));
     TRY(train_sampled_checks(h, s, iterations, batch, step, noise));
     if (iterations >= 64) try_specialize(h);
@@ -293,16 +294,11 @@ static int train_sampled_impl(gnn_mlp_t *h, gnn_sampler_t *s, int iterations, in
                 h->la.announce(NextBatch{h->DX, d_idx + sn, dcnt[(size_t)((c + 1) % kRing) * kChunk]});
             }
             rc = step_on_device_indices(h, d_idx + so + (size_t)(i - i0) * batch, ccnt[i - i0], step, momentum);
-            // (the validation pass reads the weights the step has just written; it touches neither the slabs the step's tile
+            // (a validation pass reads the weights the step has just written; it touches neither the slabs the step's tile
             //  kernel made for the next batch nor the staged rows, so the chain of two-launch steps runs on behind it)
-            if (rc == GNN_OK && d_val) {
-                // the per-sample losses of iteration i stay in row i of d_rows (summed once, behind the loop); a validation set of
-                // more than one block is summed block by block as before
-                int vrc = GNN_OK;
-                if (d_rows && validation_losses_to_row(h, validation_size, d_rows + (size_t)i * row_stride, &vrc)) rc = vrc;
-                else rc = validation_loss_sum(h, validation_size, d_val + i);
-            }
+            if (rc == GNN_OK && obs) rc = obs->after_step(i);
         }
+        if (rc == GNN_OK && obs) rc = obs->after_chunk(i1);
     }
     // (on an early exit the sampler stops after the chunk it is drawing: its state stays well defined)
     (void)hipStreamSynchronize(h->stream); // the device ring is released below
@@ -310,14 +306,32 @@ static int train_sampled_impl(gnn_mlp_t *h, gnn_sampler_t *s, int iterations, in
     return rc;
 }
 
-int gnn::host::train_sampled_run(gnn_mlp *h, gnn_sampler_t *s, int iterations, int batch, double step, double momentum, int noise) {
-    return train_sampled_impl(h, s, iterations, batch, step, momentum, noise, 0, nullptr);
+int gnn::host::train_sampled_run(gnn_mlp *h, gnn_sampler_t *s, int iterations, int batch, double step, double momentum, int noise,
+                                 SampledObserver *obs) {
+    return train_sampled_impl(h, s, iterations, batch, step, momentum, noise, obs);
 }
+
+namespace {
+// The observed variants (NNT:68-72, 75-79) of a lone handle: after iteration i the summed validation loss of rows
+// [0, validation_size) goes to d_val[i] (device).
+struct LoneValidation : SampledObserver {
+    gnn_mlp *h; int validation_size; double *d_val; float *d_rows; int64_t row_stride;
+    LoneValidation(gnn_mlp *h_, int n, double *dv, float *dr, int64_t rs) : h(h_), validation_size(n), d_val(dv), d_rows(dr), row_stride(rs) {}
+    int after_step(int i) override {
+        // the per-sample losses of iteration i stay in row i of d_rows (summed once, behind the loop); a validation set of
+        // more than one block is summed block by block as before
+        int vrc = GNN_OK;
+        if (d_rows && validation_losses_to_row(h, validation_size, d_rows + (size_t)i * row_stride, &vrc)) return vrc;
+        return validation_loss_sum(h, validation_size, d_val + i);
+    }
+};
+} // namespace
+
 extern "C" {
 
 int gnn_mlp_train_sampled(gnn_mlp_t *h, gnn_sampler_t *s, int iterations, int batch, double step, double momentum,
                           int noise) { return guarded([&]() -> int {
-    return train_sampled_impl(h, s, iterations, batch, step, momentum, noise, 0, nullptr);
+    return train_sampled_impl(h, s, iterations, batch, step, momentum, noise, nullptr);
 }); }
 
 int gnn_mlp_train_sampled_observed(gnn_mlp_t *h, gnn_sampler_t *s, int iterations, int batch, double step, double momentum,
@@ -333,7 +347,8 @@ int gnn_mlp_train_sampled_observed(gnn_mlp_t *h, gnn_sampler_t *s, int iteration
     const int64_t stride = pad_up(validation_size);
     const bool rows_form = eval_block_rows(h, validation_size) >= validation_size && (int64_t)iterations * stride * 4 <= (1ll << 30);
     if (rows_form) TRY(drows.alloc(sizeof(float) * (size_t)iterations * (size_t)stride));
-    TRY(train_sampled_impl(h, s, iterations, batch, step, momentum, noise, validation_size, dv.as<double>(), rows_form ? drows.as<float>() : nullptr, stride));
+    LoneValidation obs(h, validation_size, dv.as<double>(), rows_form ? drows.as<float>() : nullptr, stride);
+    TRY(train_sampled_impl(h, s, iterations, batch, step, momentum, noise, &obs));
     if (rows_form) {
         hipLaunchKernelGGL(sum_rows_kernel, dim3(iterations), dim3(256), 0, h->stream, RowSumParams{drows.as<float>(), stride, validation_size, dv.as<double>()});
         TRY_LAUNCHES(h);

@@ -459,6 +459,25 @@ class NetGroup:
         _capi.check(self._lib.gnn_mlp_group_train_sampled(self._h, sampler._h, int(iterations), int(batch), _dp(st), _dp(mo),
                                                           int(bool(noise))))
 
+    def train_sampled_observed(self, sampler, iterations, batch, steps, momenta, validation_size=None, noise=False):
+        """NNT:68-72 / 75-79 for every member with the draws of ONE sampler: train_sampled, and after every iteration
+        validate(validation_size) (NNT:102-113, the mean loss of the first rows of the data set; default rows // 100 + 1,
+        NNT:65) of every member.  Returns the curves, an ndarray (iterations, K), from one readback."""
+        st, mo = _per_member("steps", steps, len(self)), _per_member("momenta", momenta, len(self))
+        if validation_size is None:
+            if getattr(self, "_dataset_rows", None) is None:
+                raise ValueError("validation_size=None needs an uploaded data set")
+            validation_size = self._dataset_rows // 100 + 1
+        val = np.empty((max(int(iterations), 0), len(self)), dtype=np.float64)
+        _capi.check(self._lib.gnn_mlp_group_train_sampled_observed(self._h, sampler._h, int(iterations), int(batch), _dp(st), _dp(mo),
+                                                                   int(bool(noise)), int(validation_size), _dp(val)))
+        return val
+
+    @property
+    def observed_launches(self):
+        """3: two grouped step launches + one grouped validation launch per iteration; 0: member after member."""
+        return self._lib.gnn_mlp_group_observed_launches(self._h)
+
     @property
     def launches_per_step(self):
         """2: every launch of a group step serves all members; 0: the members are stepped one after another."""

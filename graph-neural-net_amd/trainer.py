@@ -119,6 +119,50 @@ class NeuralNetTrainer:
         return total / batchSize
 
 
+class NetGroupTrainer:
+    """NeuralNetTrainer for a NetGroup: ONE data set and ONE sampler (Random(seed), NNT:42) for every member -- the reference's
+    sweep of MNISTTrainer runs, each of which samples with Random(1), as one trainer."""
+
+    OBSERVER_BURST = NeuralNetTrainer.OBSERVER_BURST
+
+    def __init__(self, data_x, data_y, group, raw_u8=False, seed=1):
+        self.group = group
+        if raw_u8:
+            group.upload_dataset_u8(data_x, data_y)
+        else:
+            group.upload_dataset(data_x, data_y)
+        self.size = group._dataset_rows
+        self.sampler = Sampler(self.size, seed)
+
+    def train(self, iterations, stepSizes, batchSize, momenta, noise=False, monitor=None, observers=None):
+        """NNT:60-92 for every member (stepSizes / momenta: one value per member, or a scalar for all).  observers: K text
+        streams, observers[k] receiving "%d,%.2f\n" % (i, validation loss of member k) per iteration (NNT:71); monitor: an
+        object with step() / finish(), stepped once per iteration."""
+        if not iterations > 0:
+            raise ValueError("iterations must be positive (NNT:62)")
+        if not (0 < batchSize < self.size):
+            raise ValueError("batchSize must be positive and below the data size (NNT:63)")
+        if observers is not None and len(observers) != len(self.group):
+            raise ValueError("observers: one stream per member (%d), got %d" % (len(self.group), len(observers)))
+        validation_size = self.size // 100 + 1                       # NNT:65
+        done = 0
+        while done < iterations:                                     # (a monitor steps in bursts: a device loop per burst)
+            n = min(self.OBSERVER_BURST, iterations - done) if monitor is not None else iterations - done
+            if observers is None:
+                self.group.train_sampled(self.sampler, n, batchSize, stepSizes, momenta, noise)
+            else:
+                val = self.group.train_sampled_observed(self.sampler, n, batchSize, stepSizes, momenta, validation_size, noise)
+            for i in range(n):
+                if observers is not None:
+                    for k, o in enumerate(observers):
+                        o.write("%d,%.2f\n" % (done + i, val[i, k]))  # NNT:71
+                if monitor is not None:
+                    monitor.step()
+            done += n
+        if monitor is not None:
+            monitor.finish()
+
+
 # ---- MNIST (MNISTTrainer.java) ---------------------------------------------------------------
 def read_idx_images(path):
     """MT:37-47: magic 2051, count, rows, cols (big-endian int32, MT:76-80), then raw bytes."""

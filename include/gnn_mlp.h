@@ -320,6 +320,18 @@ int gnn_mlp_group_train_sampled(gnn_mlp_group_t *g, gnn_sampler_t *s, int iterat
 /* 2: every launch of a group step serves all members (the two-launch path); 0: the members are stepped one after another
  * through their own handles (nets off that path, or whose row-block kernel is middle4_kernel) -- same results, no speed-up */
 int gnn_mlp_group_launches_per_step(const gnn_mlp_group_t *g);
+/* gnn_mlp_train_sampled_observed (NNT:68-72 / 75-79) for every member with ONE sampler's draws:
+ * val_loss[i * K + k] = validate(validation_size) of member k after iteration i (iterations x K values).  One readback.
+ * The members and the sampler end as after gnn_mlp_group_train_sampled with the same arguments, bit for bit: the validation
+ * pass writes no weight, momentum, step count or look-ahead state.  validation_size outside [1, dataset rows] or a null
+ * val_loss -> GNN_ERR_BAD_ARG; noise != 0 -> GNN_ERR_UNSUPPORTED. */
+int gnn_mlp_group_train_sampled_observed(gnn_mlp_group_t *g, gnn_sampler_t *s, int iterations, int batch,
+                                         const double *steps, const double *momenta, int noise,
+                                         int validation_size, double *val_loss);
+/* 3: two grouped step launches + one grouped validation launch (per block of validation rows) per iteration, the curves summed
+ * on the device; 0: member after member, each through gnn_mlp_train_sampled_observed on its own handle (groups of one net, or
+ * without grouped step launches) -- column k is then bit for bit the lone handle's curve */
+int gnn_mlp_group_observed_launches(const gnn_mlp_group_t *g);
 int gnn_mlp_group_synchronize(gnn_mlp_group_t *g);
 /* Evaluation of a whole group in one pass (csrc/group_eval_kernel.h).
  * 2: one grouped forward launch + one combine launch per block of rows; 0: member after member */
