@@ -1,6 +1,7 @@
 // abi.hip -- the C ABI of include/gnn_mlp.h for ONE net on ONE GPU: argument checks, staging of host rows,
 // the handle's lifetime.  What a step is made of: plan.hip; kernels: launch_*.hip.
 #include "handle.h"
+#include "confusion_kernel.h"
 
 #include <algorithm>
 
@@ -646,6 +647,54 @@ int gnn_mlp_count_hits_range(gnn_mlp_t *h, int64_t first, int64_t n, int64_t *hi
     HIP_TRY(hipMemcpyAsync(&got, cnt.p, sizeof(got), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     *hits = (int64_t)got;
+    return GNN_OK;
+}); }
+
+// count_hits_range's block loop with everything an evaluation pass has on the device counted in it: the hits, the loss sum
+// (validate() of NNT:102-113 without its division; sum_loss_kernel block after block into ONE slot: one fixed order, the same
+// bits every time) and the confusion matrix of the labels (confusion_kernel.h, one table), the labels themselves on request.
+int gnn_mlp_evaluate_range(gnn_mlp_t *h, int64_t first, int64_t n, int64_t *hits, double *loss_sum, int64_t *confusion,
+                           int32_t *labels) { return guarded([&]() -> int {
+    TRY(check_handle(h));
+    if (!hits && !loss_sum && !confusion && !labels) return fail(GNN_ERR_BAD_ARG, "every output is null");
+    if (!h->DX) return fail(GNN_ERR_STATE, "no dataset uploaded");
+    if (n <= 0 || first < 0 || first + n > h->dataset_n) return fail(GNN_ERR_BAD_ARG, "rows outside the dataset");
+    const int Lm = h->L - 1, d_out = h->dims[Lm];
+    // [hit counter][loss sum][d_out x d_out counters][n labels]: one fill, one readback
+    const size_t cells = (size_t)d_out * d_out;
+    const size_t head = sizeof(unsigned long long) * (2 + cells), lab_b = labels ? sizeof(int32_t) * (size_t)n : 0;
+    DevScratch res;
+    TRY(res.alloc(head + lab_b));
+    HIP_TRY(hipMemsetAsync(res.p, 0, head, h->stream));
+    unsigned long long *d_hits = res.as<unsigned long long>();
+    static_assert(sizeof(unsigned long long) == sizeof(double), "one buffer for counters and the sum");
+    double *d_loss = reinterpret_cast<double *>(d_hits + 1);
+    const int block = eval_block_rows(h, n);
+    int rc_ws = GNN_OK;
+    EvalScope scope(h, block, &rc_ws);
+    if (rc_ws != GNN_OK) return rc_ws;
+    for (int64_t off = 0; off < n; off += block) {
+        const int B = (int)std::min<int64_t>(block, n - off);
+        const float *y = h->DY + (size_t)(first + off) * h->ld[Lm];
+        do_forward(h, h->DX + (size_t)(first + off) * h->ld[0], y, B, false, true, true);
+        hipLaunchKernelGGL(count_hits_kernel, dim3((B + 255) / 256), dim3(256), 0, h->stream,
+                           HitsParams{h->labels, y, h->ld[Lm], d_out, B, d_hits});
+        hipLaunchKernelGGL(sum_loss_kernel, dim3(1), dim3(256), 0, h->stream, LossSumParams{h->lossv, B, d_loss, off > 0 ? 1 : 0});
+        ConfusionParams cf{};
+        cf.label[0] = h->labels; cf.T = 1; cf.rows = B; cf.n_out = d_out; cf.Y = y; cf.ldy = h->ld[Lm];
+        cf.counts = d_hits + 2;
+        cf.labels_out = labels ? reinterpret_cast<int32_t *>(res.as<char>() + head) : nullptr;
+        cf.T_copy = 1; cf.out_stride = n; cf.row_offset = off;
+        HIP_TRY(launch_confusion(cf, h->stream));
+    }
+    TRY_LAUNCHES(h);
+    std::vector<unsigned long long> host((head + lab_b + 7) / 8);
+    HIP_TRY(hipMemcpyAsync(host.data(), res.p, head + lab_b, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (hits) *hits = (int64_t)host[0];
+    if (loss_sum) std::memcpy(loss_sum, &host[1], sizeof(double));
+    if (confusion) for (size_t i = 0; i < cells; i++) confusion[i] = (int64_t)host[2 + i];
+    if (labels) std::memcpy(labels, reinterpret_cast<const char *>(host.data()) + head, lab_b);
     return GNN_OK;
 }); }
 

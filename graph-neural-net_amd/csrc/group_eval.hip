@@ -6,10 +6,13 @@
 // the members run one after another, each its own do_forward under its EvalScope in blocks of its own eval_block_rows, and
 // the same combine kernel reads the members' own prob / lossv / labels buffers: the same results up to near-ties, no speed-up.
 // Evaluation writes no weight, no momentum, no step count and no look-ahead state.
+// gnn_mlp_group_confusion_range is the same pass with one more launch per block behind the combine kernel: confusion_kernel
+// (confusion_kernel.h) over the label tables the combine kernel just read and the ensemble's labels it just wrote.
 //
 // The validation pass of a group's observed training loop (group.hip: gnn_mlp_group_train_sampled_observed) is enqueued from
 // here too: the forward kernel's LOSS_ONLY form into a row of the curve matrix, and group_curve_sum_kernel over that matrix.
 #include "handle.h"
+#include "confusion_kernel.h"
 
 #include <algorithm>
 #include <memory>
@@ -87,6 +90,8 @@ GroupEvalParams forward_params(const gnn_mlp_group *g, int64_t first, int B) {
 struct EvalOut { // device results of one call
     unsigned long long *hits; double *sums; double *slots; // [K + 1], [K], [n_slots][GE_GROUP_MAX]
     float *mean; int32_t *ens_label;                       // [n][d_out], [n] or null
+    unsigned long long *confusion = nullptr;               // [K + 1][d_out][d_out] or null: the members', then the ensemble's (needs ens_label)
+    int32_t *member_labels = nullptr;                      // [K][n] or null (with confusion only)
 };
 
 // rows [first, first + n) in blocks: forward (grouped or member after member), then the combine kernel
@@ -146,6 +151,15 @@ int run_blocks(gnn_mlp_group *g, int64_t first, int64_t n, const EvalOut &o) {
         hipLaunchKernelGGL(group_combine_kernel, dim3((unsigned)nb), dim3(256), 0, h0->stream, cp);
         HIP_TRY(hipGetLastError());
         slot += nb;
+        if (o.confusion) { // the tables the combine kernel just read, then the ensemble's labels of this block
+            ConfusionParams cf{};
+            for (int k = 0; k < g->K; k++) cf.label[k] = cp.label[k];
+            cf.label[g->K] = cp.ens_label;
+            cf.T = g->K + 1; cf.rows = B; cf.n_out = d_out; cf.Y = y; cf.ldy = ldo;
+            cf.counts = o.confusion;
+            cf.labels_out = o.member_labels; cf.T_copy = g->K; cf.out_stride = n; cf.row_offset = off;
+            HIP_TRY(launch_confusion(cf, h0->stream));
+        }
     }
     hipLaunchKernelGGL(group_loss_finish_kernel, dim3(1), dim3(64), 0, h0->stream, o.slots, slot, g->K, o.sums);
     HIP_TRY(hipGetLastError());
@@ -279,6 +293,41 @@ int gnn_mlp_group_ensemble_range(gnn_mlp_group_t *g, int64_t first, int64_t n, d
         for (size_t i = 0; i < (size_t)n * d_out; i++) mean_out[i] = (double)src[i];
     }
     if (labels) std::memcpy(labels, host.data() + mean_b, lab_b);
+    return GNN_OK;
+}); }
+
+int gnn_mlp_group_confusion_range(gnn_mlp_group_t *g, int64_t first, int64_t n, int64_t *member_confusion,
+                                  int64_t *ensemble_confusion, int32_t *member_labels) { return guarded([&]() -> int {
+    if (!g) return fail(GNN_ERR_BAD_ARG, "null group");
+    if (!member_confusion && !ensemble_confusion && !member_labels) return fail(GNN_ERR_BAD_ARG, "every output is null");
+    TRY(check_eval_args(g, first, n));
+    const gnn_mlp *h0 = g->m[0];
+    const int K = g->K, ns = n_slots_for(g, n), d_out = h0->dims[h0->L - 1];
+    const size_t cells = (size_t)d_out * d_out;
+    // the loss slots | [K + 1] hit counters, [K] loss sums, [K + 1] matrices (one fill) | the members' labels (with the
+    // matrices: one readback) | the ensemble's labels
+    const size_t slots_b = sizeof(double) * (size_t)ns * GE_GROUP_MAX;
+    const size_t head = sizeof(unsigned long long) * (size_t)(K + 1) + sizeof(double) * (size_t)K;
+    const size_t conf_b = sizeof(unsigned long long) * (size_t)(K + 1) * cells;
+    const size_t lab_b = member_labels ? sizeof(int32_t) * (size_t)K * (size_t)n : 0, ens_b = sizeof(int32_t) * (size_t)n;
+    DevScratch res;
+    TRY(res.alloc(slots_b + head + conf_b + lab_b + ens_b));
+    hipStream_t st = h0->stream;
+    HIP_TRY(hipMemsetAsync(res.as<char>() + slots_b, 0, head + conf_b, st));
+    EvalOut o{};
+    o.slots = res.as<double>();
+    o.hits = reinterpret_cast<unsigned long long *>(res.as<char>() + slots_b);
+    o.sums = reinterpret_cast<double *>(o.hits + (K + 1));
+    o.confusion = reinterpret_cast<unsigned long long *>(res.as<char>() + slots_b + head);
+    o.member_labels = member_labels ? reinterpret_cast<int32_t *>(res.as<char>() + slots_b + head + conf_b) : nullptr;
+    o.ens_label = reinterpret_cast<int32_t *>(res.as<char>() + slots_b + head + conf_b + lab_b);
+    TRY(run_blocks(g, first, n, o));
+    std::vector<unsigned long long> host((conf_b + lab_b + 7) / 8);
+    HIP_TRY(hipMemcpyAsync(host.data(), o.confusion, conf_b + lab_b, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (member_confusion) for (size_t i = 0; i < (size_t)K * cells; i++) member_confusion[i] = (int64_t)host[i];
+    if (ensemble_confusion) for (size_t i = 0; i < cells; i++) ensemble_confusion[i] = (int64_t)host[(size_t)K * cells + i];
+    if (member_labels) std::memcpy(member_labels, reinterpret_cast<const char *>(host.data()) + conf_b, lab_b);
     return GNN_OK;
 }); }
 

@@ -233,6 +233,41 @@ class NeuralNet:
         _capi.check(self._lib.gnn_mlp_count_hits_range(self._h, int(first), n, C.byref(out)))
         return out.value
 
+    # the same pass with what it has on the device returned: gnn_mlp_evaluate_range (one call, one readback, any n)
+    def _rows(self, first, n):
+        first = int(first)
+        if n is None:
+            size = self.dataset_size
+            if size <= 0:
+                raise ValueError("n=None needs an uploaded data set")
+            n = size - first
+        return first, int(n)
+
+    def evaluate_range(self, first=0, n=None):
+        """(hits, loss_sum) over dataset rows [first, first + n): count_hits_range's count (MT:159-197) and the sum of
+        calculateLoss over the rows (validate(), NNT:102-113, without its division)."""
+        first, n = self._rows(first, n)
+        hits, loss = C.c_int64(), C.c_double()
+        _capi.check(self._lib.gnn_mlp_evaluate_range(self._h, first, n, C.byref(hits), C.byref(loss), None, None))
+        return hits.value, loss.value
+
+    def confusion_range(self, first=0, n=None):
+        """The confusion matrix of the rows, (d_out, d_out) int64: entry [e, p] counts the rows whose expected class (the last
+        index whose expected value is 1, MT:186-188) is e and whose `>=` argmax (MT:166-168) is p.  Exact; its trace is
+        count_hits_range's count."""
+        first, n = self._rows(first, n)
+        d = self.layer_dims[-1]
+        conf = np.zeros((d, d), dtype=np.int64)
+        _capi.check(self._lib.gnn_mlp_evaluate_range(self._h, first, n, None, None, conf.ctypes.data_as(C.POINTER(C.c_int64)), None))
+        return conf
+
+    def labels_range(self, first=0, n=None):
+        """argmax_range for any number of rows: int32[n], the labels count_hits_range and confusion_range count."""
+        first, n = self._rows(first, n)
+        lab = np.empty(max(n, 0), dtype=np.int32)
+        _capi.check(self._lib.gnn_mlp_evaluate_range(self._h, first, n, None, None, None, lab.ctypes.data_as(C.POINTER(C.c_int32))))
+        return lab
+
     # -- data-parallel hooks ------------------------------------------------------------------
     @property
     def grad_elems(self):
@@ -526,6 +561,21 @@ class NetGroup:
         lab = np.empty(max(n, 0), dtype=np.int32)
         _capi.check(self._lib.gnn_mlp_group_ensemble_range(self._h, first, n, None, lab.ctypes.data_as(C.POINTER(C.c_int32))))
         return lab
+
+    def confusion_range(self, first=0, n=None, labels=False):
+        """(member (K, d, d), ensemble (d, d)) int64 confusion matrices over the rows -- entry [e, p]: expected class e (MT:186-188),
+        predicted class p, member k's `>=` argmax or the argmax of the mean output -- from the pass of evaluate_range and one
+        readback; with labels=True also the members' labels (K, n) int32 the counts were made from."""
+        first, n = self._rows(first, n)
+        k, d = len(self), self.layer_dims[-1]
+        member = np.zeros((k, d, d), dtype=np.int64)
+        ens = np.zeros((d, d), dtype=np.int64)
+        lab = np.empty((k, max(n, 0)), dtype=np.int32) if labels else None
+        i64 = C.POINTER(C.c_int64)
+        _capi.check(self._lib.gnn_mlp_group_confusion_range(
+            self._h, first, n, member.ctypes.data_as(i64), ens.ctypes.data_as(i64),
+            lab.ctypes.data_as(C.POINTER(C.c_int32)) if labels else None))
+        return (member, ens, lab) if labels else (member, ens)
 
 
 class DataParallelNeuralNet:

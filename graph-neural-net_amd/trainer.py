@@ -110,13 +110,10 @@ class NeuralNetTrainer:
                 observer.write("%d,%.2f\n" % (i, self.validate(validation_size)))
 
     def validate(self, batchSize):
-        """NNT:102-113: mean loss over the first batchSize samples in master order."""
-        total, first = 0.0, 0
-        while first < batchSize:
-            n = min(self.net.max_batch, batchSize - first)
-            total += float(self.net.loss_range(first, n).sum())
-            first += n
-        return total / batchSize
+        """NNT:102-113: mean loss over the first batchSize samples in master order.  One call and one readback
+        (NeuralNet.evaluate_range): the rows' f32 losses are summed in fp64 on the device, so the value is that of a host sum of
+        loss_range over blocks of max_batch up to the fp64 order of the per-row sum."""
+        return self.net.evaluate_range(0, batchSize)[1] / batchSize
 
 
 class NetGroupTrainer:
@@ -202,6 +199,18 @@ def accuracy(net, labels=None, first=0, n=None):
         hits += int((net.argmax_range(first + off, n) == labels[off:off + n]).sum())
         off += n
     return hits / labels.size
+
+
+def per_class(conf):
+    """(recall[d], precision[d]) of a confusion matrix conf[expected, predicted]: recall[c] = conf[c, c] / (rows expecting c),
+    precision[c] = conf[c, c] / (rows predicted c); NaN where that row or column is empty."""
+    conf = np.asarray(conf, dtype=np.float64)
+    if conf.ndim != 2 or conf.shape[0] != conf.shape[1]:
+        raise ValueError("expected a square matrix, got shape %r" % (conf.shape,))
+    diag, rows, cols = np.diag(conf), conf.sum(axis=1), conf.sum(axis=0)
+    recall = np.where(rows > 0, diag / np.where(rows > 0, rows, 1.0), np.nan)
+    precision = np.where(cols > 0, diag / np.where(cols > 0, cols, 1.0), np.nan)
+    return recall, precision
 
 
 def train_log_row(net_dim, iterations, step_size, batch_size, momentum, noise, training_acc, test_acc):

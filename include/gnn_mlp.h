@@ -167,6 +167,14 @@ int gnn_mlp_argmax_range(gnn_mlp_t *h, int64_t first, int B, int32_t *labels);
  * (MT:186-188; for the one-hot rows of MT:112-118 that is the label).  The rows are walked in blocks of max_batch with no host
  * work in between; ONE count comes back.  The reference returns hits / size (MT:172, 197): the division is the caller's. */
 int gnn_mlp_count_hits_range(gnn_mlp_t *h, int64_t first, int64_t n, int64_t *hits);
+/* The same pass (MT:159-197) with everything it has on the device returned from ONE readback, any n: *hits as
+ * gnn_mlp_count_hits_range counts them; *loss_sum = the sum of calculateLoss over the rows (validate() of NNT:102-113 without its
+ * division), added block after block in one fixed order; confusion[e * d_out + p] = the number of rows whose expected class
+ * (MT:186-188) is e and whose `>=` argmax (MT:166-168) is p -- row = expected, column = predicted, the trace is *hits --;
+ * labels[i] = the argmax of row first + i.  Each of the four may be null, not all of them.  Works on borrowed handles (group
+ * members, data-parallel replicas); bf16 handles walk blocks of max_batch rows. */
+int gnn_mlp_evaluate_range(gnn_mlp_t *h, int64_t first, int64_t n, int64_t *hits, double *loss_sum,
+                           int64_t *confusion /* [d_out][d_out] */, int32_t *labels /* [n] */);
 
 /* ---- the trainer's sampling loop (NeuralNetTrainer.java) ------------------------------------ */
 
@@ -344,6 +352,14 @@ int gnn_mlp_group_evaluate_range(gnn_mlp_group_t *g, int64_t first, int64_t n, i
 /* the ensemble's propagate() and argmax over the same rows: mean_out is n x d_out (fp64 of the f32 mean), labels has n entries;
  * either may be null, not both */
 int gnn_mlp_group_ensemble_range(gnn_mlp_group_t *g, int64_t first, int64_t n, double *mean_out, int32_t *labels);
+/* Confusion matrices of the same pass (MT:159-197; the loss pass of NNT:102-113 runs with it and is not returned):
+ * member_confusion[(k * d_out + e) * d_out + p] = rows whose expected class (MT:186-188) is e and on which member k's `>=` argmax
+ * is p; ensemble_confusion the same for the argmax of the mean output; member_labels[k * n + i] = member k's argmax of row
+ * first + i, the labels the counts were made from.  Each of the three may be null, not all of them.  One more launch per
+ * block of rows behind the combine kernel (csrc/confusion_kernel.h), one readback; exact integer counts.  Writes no weight,
+ * momentum, step count or look-ahead state; each member's deferred host-batch update is applied first. */
+int gnn_mlp_group_confusion_range(gnn_mlp_group_t *g, int64_t first, int64_t n, int64_t *member_confusion /* [K][d_out][d_out] */,
+                                  int64_t *ensemble_confusion /* [d_out][d_out] */, int32_t *member_labels /* [K][n] */);
 
 /* ---- shape specialisation ---------------------------------------------------------------------
  * The per-row-block kernel of the fused small-net path is a template over the net's shape; with
