@@ -6,8 +6,9 @@
 // member 0's kernel arguments into member k's.  A group step then drives MEMBER 0's control path (plan.hip: chain_gradient,
 // launch_small.hip) with GroupLaunch set, which turns each of its two launches into the grouped launch -- there is no second
 // copy of the chain logic.  What a step reads and every member shares -- the dataset, the device index ring of a sampled
-// call -- is member 0's and lies outside the arena.  Nets off the two-launch path are stepped one member after another
-// through their own handles: the same results, no speed-up.
+// call -- is member 0's and lies outside the arena.  (A call with one sampler per member keeps K index rings in one region
+// outside the arena, a second relocatable range: the end of this file.)  Nets off the two-launch path are stepped one member
+// after another through their own handles: the same results, no speed-up.
 #include "handle.h"
 
 #include <algorithm>
@@ -38,11 +39,12 @@ int enter_grouped(gnn_mlp_group *g) {
         for (int k = 0; k < g->K; k++) { g->m[k]->la = g->m[0]->la.rebased(g->arena, g->S, k); g->m[k]->la.forget(); } // (one staging buffer index for all)
     return GNN_OK;
 }
-// After it: member 0's step count and look-ahead state, moved to each member
-void leave_grouped(gnn_mlp_group *g, int steps_done) {
+// After it: member 0's step count and look-ahead state, moved to each member.  (idx_lo, idx_S: the index region of a call
+// with one sampler per member while it is live -- lookahead.h.)
+void leave_grouped(gnn_mlp_group *g, int steps_done, const char *idx_lo = nullptr, size_t idx_S = 0) {
     for (int k = 1; k < g->K; k++) {
         g->m[k]->time += steps_done;
-        g->m[k]->la = g->m[0]->la.rebased(g->arena, g->S, k);
+        g->m[k]->la = g->m[0]->la.rebased(g->arena, g->S, k, idx_lo, idx_S);
     }
 }
 
@@ -225,7 +227,7 @@ int gnn_mlp_group_train_sampled(gnn_mlp_group_t *g, gnn_sampler_t *s, int iterat
     return rc;
 }); }
 
-/* The observed loop (NNT:68-72 / 75-79) of a group: the sampled loop above with, behind every step and still under the
+/* The observed loop (NNT:68-72 / 75-79) of a group: the sampled loops with, behind every step and still under the
  * GroupScope, ONE launch of the forward kernel's validation form per block of validation rows (group_eval.hip) -- the members'
  * per-row losses of iteration i go to row i mod M of a matrix [M][K][stride], which ONE launch of group_curve_sum_kernel turns
  * into d_val[i][k] whenever it is full and behind the last step.  Everything is allocated and checked before the first step. */
@@ -296,5 +298,111 @@ int gnn_mlp_group_train_sampled_observed(gnn_mlp_group_t *g, gnn_sampler_t *s, i
     for (size_t i = 0; i < (size_t)iterations * K; i++) val_loss[i] /= (double)validation_size; // NNT:112
     return GNN_OK;
 }); }
+
+} // extern "C"
+
+/* One sampler per member.  The loop is train_sampled_impl's on member 0 with K index rings (sampler.hip); an iteration in
+ * which every member's batch has the same size is the two grouped launches, member k reading ring k through the index region
+ * (group_kernels.h).  A refill shortens a batch per member (NNT:149-155), so around a refill the sizes may differ: such a
+ * MIXED iteration is stepped member after member through the members' own handles, outside the GroupScope -- the lone step by
+ * construction.  Nothing is announced for it and every member's look-ahead state is forgotten on both sides of it (bitwise
+ * neutral: one forward-only launch when the grouped chain resumes). */
+namespace {
+struct EachMember : SampledEach {
+    gnn_mlp_group *g; GroupLaunch *gl; const double *steps, *momenta;
+    size_t slice_elems = 0;
+    int64_t mixed = 0;
+    ~EachMember() override { if (gl->idx_lo) region(nullptr, 0); } // (the loop was left by an exception)
+    void region(const int32_t *lo, size_t slice_bytes) override {
+        if (!lo) { // about to be released: no member keeps an address inside it
+            leave_grouped(g, 0, gl->idx_lo, gl->idx_S);
+            for (gnn_mlp *h : g->m) h->la.index_region_released();
+        }
+        gl->idx_lo = reinterpret_cast<const char *>(lo); gl->idx_S = slice_bytes;
+        slice_elems = slice_bytes / sizeof(int32_t);
+    }
+    void forget_all() { // member 0's state for everyone (one staging buffer index for all), then forgotten
+        for (int k = 0; k < g->K; k++) { g->m[k]->la = g->m[0]->la.rebased(g->arena, g->S, k, gl->idx_lo, gl->idx_S); g->m[k]->la.forget(); }
+    }
+    int mixed_step(const int32_t *d_idx0, const int *counts) override {
+        gnn_mlp *h0 = g->m[0];
+        h0->grp = nullptr; // (outside the GroupScope; set again below on every path)
+        forget_all();
+        int rc = GNN_OK;
+        for (int k = 0; k < g->K && rc == GNN_OK; k++)
+            rc = step_on_device_indices(g->m[k], d_idx0 + (size_t)k * slice_elems, counts[k], steps[k], momenta[k]);
+        forget_all();
+        h0->grp = gl;
+        mixed++;
+        return rc;
+    }
+};
+} // namespace
+
+extern "C" {
+
+int gnn_mlp_group_train_sampled_each(gnn_mlp_group_t *g, gnn_sampler_t *const *samplers, int iterations, int batch,
+                                     const double *steps, const double *momenta, int noise, int validation_size,
+                                     double *val_loss) { return guarded([&]() -> int {
+    TRY(check_group(g));
+    TRY(check_per_member(g, steps, momenta));
+    const int K = g->K;
+    gnn_mlp *h0 = g->m[0];
+    if (!samplers) return fail(GNN_ERR_BAD_ARG, "samplers is null");
+    for (int k = 0; k < K; k++) if (!samplers[k]) return fail(GNN_ERR_BAD_ARG, "null sampler");
+    for (int k = 0; k < K; k++)
+        for (int j = 0; j < k; j++)
+            if (samplers[j] == samplers[k]) return fail(GNN_ERR_BAD_ARG, "the same sampler for two members: every member draws from its own");
+    for (int k = 0; k < K; k++) TRY(train_sampled_checks(g->m[k], samplers[k], iterations, batch, steps[k], noise));
+    if (val_loss && (validation_size <= 0 || validation_size > h0->dataset_n)) return fail(GNN_ERR_BAD_ARG, "validation size outside the dataset (NNT:104)");
+    g->each_grouped = g->each_mixed = 0;
+    const bool fallback = K == 1 || !g->grouped || (val_loss && gnn_mlp_group_observed_launches(g) != 3);
+    if (fallback) { // member after member, each with its own sampler through its own handle
+        std::vector<double> col(val_loss ? (size_t)iterations : 0);
+        for (int k = 0; k < K; k++) {
+            if (!val_loss) { TRY(gnn_mlp_train_sampled(g->m[(size_t)k], samplers[k], iterations, batch, steps[k], momenta[k], noise)); continue; }
+            TRY(gnn_mlp_train_sampled_observed(g->m[(size_t)k], samplers[k], iterations, batch, steps[k], momenta[k], noise, validation_size, col.data()));
+            for (int i = 0; i < iterations; i++) val_loss[(size_t)i * K + k] = col[(size_t)i];
+        }
+        g->each_mixed = iterations;
+        return GNN_OK;
+    }
+    GroupValidation obs;
+    DevScratch rows, val;
+    if (val_loss) {
+        obs.g = g; obs.validation_size = validation_size; obs.iterations = iterations;
+        obs.M = std::min(iterations, kCurveRows); obs.stride = pad_up(validation_size);
+        TRY(rows.alloc(sizeof(float) * (size_t)obs.M * K * (size_t)obs.stride));
+        TRY(val.alloc(sizeof(double) * (size_t)iterations * K));
+        obs.d_rows = rows.as<float>(); obs.d_val = val.as<double>();
+    }
+    TRY(enter_grouped(g));
+    GroupLaunch gl;
+    TRY(group_launch(g, steps, momenta, &gl));
+    EachMember each;
+    each.g = g; each.gl = &gl; each.steps = steps; each.momenta = momenta;
+    const int t0 = h0->time;
+    int rc;
+    {
+        GroupScope scope(h0, &gl);
+        rc = train_sampled_run_each(h0, samplers, K, iterations, batch, steps[0], momenta[0], noise, val_loss ? &obs : nullptr, &each);
+    }
+    const int done = h0->time - t0;
+    // (a mixed iteration advanced every member's step count through its own handle: only the grouped ones are member 0's alone)
+    leave_grouped(g, done - (int)each.mixed);
+    g->each_mixed = each.mixed; g->each_grouped = done - each.mixed;
+    TRY(rc);
+    if (val_loss) {
+        HIP_TRY(hipMemcpy(val_loss, val.p, sizeof(double) * (size_t)iterations * K, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < (size_t)iterations * K; i++) val_loss[i] /= (double)validation_size; // NNT:112
+    }
+    return GNN_OK;
+}); }
+
+int gnn_mlp_group_sampled_each_iterations(const gnn_mlp_group_t *g, int64_t *grouped, int64_t *member_after_member) {
+    if (!g || !grouped || !member_after_member) return GNN_ERR_BAD_ARG;
+    *grouped = g->each_grouped; *member_after_member = g->each_mixed;
+    return GNN_OK;
+}
 
 } // extern "C"

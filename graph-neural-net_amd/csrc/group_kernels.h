@@ -4,8 +4,14 @@
 // The pointer rule.  Every per-member device buffer a training launch touches is carved out of one arena, member k's slice
 // at member 0's + k * S (group.hip), so a grouped launch takes member 0's parameters exactly as the single-net host code
 // builds them and member k turns each pointer p into p + k * S when (p - arena_lo) < S (unsigned), and leaves it alone
-// otherwise: what all members share -- the group's data set, the device index ring of a sampled call -- lies outside the
-// arena.  Null stays null.  The arithmetic is the single-net kernels' (the same bodies), run at a different blockIdx.
+// otherwise: what all members share -- the group's data set, the device index ring of a call with one shared sampler --
+// lies outside the arena.  Null stays null.  The arithmetic is the single-net kernels' (the same bodies), run at a different
+// blockIdx.
+//
+// The index region.  A call with one sampler per member (gnn_mlp_group_train_sampled_each) keeps K device index rings in one
+// allocation outside the arena, member 0's in [idx_lo, idx_lo + idx_S), member k's the same layout at + k * idx_S.  For the
+// INDEX pointers only (row_idx, copy_idx, next_idx) a pointer inside member 0's ring moves by k * idx_S; any other index
+// pointer (a member's idxbuf lies in the arena) follows the arena rule.  idx_S == 0 -- every other call -- matches nothing.
 #pragma once
 #include "rowblock_kernel.h"
 #include "tile_step_kernel.h"
@@ -17,6 +23,8 @@ constexpr int GROUP_MAX = 16; // members of one group (include/gnn_mlp.h: gnn_ml
 struct GroupArgs {
     const char *arena_lo;         // member 0's slice of the arena
     unsigned long long S;         // bytes per member
+    const char *idx_lo;           // member 0's slice of the index region (below); beside arena_lo / S: one cache line, one load
+    unsigned long long idx_S;     // bytes per member; 0: no region
     int nbx;                      // live workgroups per member along x (the grid is padded to a multiple of 8: XCD placement)
     float step_over_b[GROUP_MAX]; // (float)(step_k / (double)B), as step_on_rows computes it
     float momentum[GROUP_MAX];
@@ -27,10 +35,24 @@ template <class T> __device__ __forceinline__ T *group_rel(T *q, const GroupArgs
     const unsigned long long d = (unsigned long long)reinterpret_cast<const char *>(q) - (unsigned long long)g.arena_lo;
     return d < g.S ? reinterpret_cast<T *>((unsigned long long)q + shift) : q;
 }
+// ... of an index pointer: the index region first, else the arena rule (wave-uniform scalar arithmetic on kernel arguments)
+__device__ __forceinline__ const int32_t *group_rel_idx(const int32_t *q, const GroupArgs &g, unsigned long long shift) {
+    const unsigned long long a = (unsigned long long)reinterpret_cast<const char *>(q);
+    // (masks, not selects: the row-block kernel's first index load waits for this)
+    const unsigned long long in_idx = 0ull - (unsigned long long)(a - (unsigned long long)g.idx_lo < g.idx_S);
+    const unsigned long long in_arena = 0ull - (unsigned long long)(a - (unsigned long long)g.arena_lo < g.S);
+    return reinterpret_cast<const int32_t *>(a + ((in_idx & ((unsigned long long)blockIdx.y * g.idx_S)) | (~in_idx & in_arena & shift)));
+}
+// The tile bodies relocate a pointer at each use, inside their loops, and their two index pointers are p.row_idx and
+// p.next_idx: both are relocated ONCE at the kernel's top (GroupIdx), and a use picks its copy by comparing addresses -- equal
+// addresses have equal copies, so the choice is exact whichever of the two fields the body names.
+struct GroupIdx { const int32_t *row0, *row, *next; };
+template <class T> __device__ __forceinline__ T *group_rel(T *q, const GroupArgs &g, unsigned long long shift, const GroupIdx &) { return group_rel(q, g, shift); }
+__device__ __forceinline__ const int32_t *group_rel(const int32_t *q, const GroupArgs &, unsigned long long, const GroupIdx &ix) { return q == ix.row0 ? ix.row : ix.next; }
 
 // the tile kernel bodies (tile_step_body.inc) for member blockIdx.y: its pointers, its step and momentum
 #define TS_BID blockIdx.x
-#define TS_REL(q) group_rel((q), ga, ga_shift)
+#define TS_REL(q) group_rel((q), ga, ga_shift, ga_idx)
 #define TS_REL_LAYER(L) (L.A = TS_REL(L.A), L.D = TS_REL(L.D), L.W = TS_REL(L.W), L.V = TS_REL(L.V), L.G = TS_REL(L.G))
 #define TS_STEP_OVER_B ga.step_over_b[blockIdx.y]
 #define TS_MOMENTUM ga.momentum[blockIdx.y]
@@ -38,12 +60,14 @@ template <int GSRC, int GDST, bool FWD>
 __global__ __launch_bounds__(TS_THREADS) void tile_step_group_kernel(TileStepParams p, GroupArgs ga) {
     static_assert(GSRC <= 2, "grouped tile kernels: single-GPU forms only");
     const unsigned long long ga_shift = (unsigned long long)blockIdx.y * ga.S;
+    const GroupIdx ga_idx{p.row_idx, group_rel_idx(p.row_idx, ga, ga_shift), group_rel_idx(p.next_idx, ga, ga_shift)};
 #include "tile_step_body.inc"
 }
 template <int GSRC, int GDST, bool FWD>
 __global__ __launch_bounds__(TS_THREADS) void tile_step_bf16_group_kernel(TileStepParams p, GroupArgs ga) {
     static_assert(GSRC <= 2, "grouped tile kernels: single-GPU forms only");
     const unsigned long long ga_shift = (unsigned long long)blockIdx.y * ga.S;
+    const GroupIdx ga_idx{p.row_idx, group_rel_idx(p.row_idx, ga, ga_shift), group_rel_idx(p.next_idx, ga, ga_shift)};
 #include "tile_step_bf16_body.inc"
 }
 #undef TS_BID
@@ -58,7 +82,7 @@ __global__ __launch_bounds__(RB_NT) void rowblock_group_kernel(GNN_RB_HEAD_PARAM
     static_assert(!BF || SH::kL == 3 || SH::kL == 4, "the bf16 row-block kernel: nets of three and four layers");
     if ((int)blockIdx.x >= g.nbx) return;
     const unsigned long long sh = (unsigned long long)blockIdx.y * g.S;
-    p.slabs = group_rel(slabs, g, sh); p.row_idx = group_rel(row_idx, g, sh); p.copy_idx = group_rel(copy_idx, g, sh);
+    p.slabs = group_rel(slabs, g, sh); p.row_idx = group_rel_idx(row_idx, g, sh); p.copy_idx = group_rel_idx(copy_idx, g, sh);
 #pragma unroll
     for (int l = 0; l < MAX_LAYERS; l++) {
         p.W[l] = group_rel(p.W[l], g, sh); p.act[l] = group_rel(p.act[l], g, sh); p.delta[l] = group_rel(p.delta[l], g, sh);

@@ -35,6 +35,8 @@ static GroupArgs group_args(const GroupLaunch &g, int nbx, int B) {
     a.arena_lo = g.arena_lo;
     a.S = g.S;
     a.nbx = nbx;
+    a.idx_lo = g.idx_lo;
+    a.idx_S = g.idx_S;
     for (int k = 0; k < g.K; k++) { // (as step_on_rows: the caller's step over THIS batch's size)
         a.step_over_b[k] = (float)(g.step[k] / (double)B);
         a.momentum[k] = (float)g.momentum[k];

@@ -38,6 +38,7 @@ struct GroupLaunch {
     const char *arena_lo = nullptr; size_t S = 0;
     const void *rb_fn = nullptr; // the grouped row-block kernel of the net (rb_group_function)
     double step[GROUP_MAX] = {}, momentum[GROUP_MAX] = {};
+    const char *idx_lo = nullptr; size_t idx_S = 0; // the device index region of a call with one sampler per member (else 0)
 };
 } // namespace host
 } // namespace gnn
@@ -191,6 +192,7 @@ struct gnn_mlp_group {
     struct EvalPlan { bool ok = false; int mt = 0; gnn::GroupEvalLds lds{}; const void *fn = nullptr, *fn_loss = nullptr; } eval_plan; // (fn_loss: the LOSS_ONLY twin)
     float *eval_ws = nullptr;
     int eval_ws_rows = 0;
+    int64_t each_grouped = 0, each_mixed = 0; // of the last gnn_mlp_group_train_sampled_each call: iterations by grouped launches / member after member
 };
 
 namespace gnn {
@@ -437,6 +439,17 @@ struct SampledObserver {
 };
 int train_sampled_run(gnn_mlp *h, gnn_sampler_t *s, int iterations, int batch, double step, double momentum, int noise,
                       SampledObserver *obs = nullptr);
+// The group's side of the loop with ONE SAMPLER PER MEMBER (group.hip: gnn_mlp_group_train_sampled_each), run on member 0's handle:
+// region(lo, slice_bytes) when the device index region exists (member m's ring at lo + m * slice_bytes) and region(null, 0)
+// just before it is released; mixed_step(d_idx0, counts) steps ONE iteration whose batch sizes counts[m] differ between the
+// members -- member m's indices at d_idx0 + m * slice -- and leaves member 0's handle ready for the next grouped step.
+struct SampledEach {
+    virtual void region(const int32_t *lo, size_t slice_bytes) = 0;
+    virtual int mixed_step(const int32_t *d_idx0, const int *counts) = 0;
+    virtual ~SampledEach() {}
+};
+int train_sampled_run_each(gnn_mlp *h, gnn_sampler_t *const *samplers, int n, int iterations, int batch, double step, double momentum,
+                           int noise, SampledObserver *obs, SampledEach *each);
 gnn_sampler_t *sampler_copy(const gnn_sampler_t *s);
 void sampler_assign(gnn_sampler_t *dst, const gnn_sampler_t *src);
 

@@ -44,15 +44,25 @@ struct Lookahead {
 
     // Groups (group.hip): member k's buffers lie at member 0's + k * S, member 0's inside the arena slice [lo, lo + S); what every
     // member shares (the dataset, the device index ring) lies outside and keeps its address.  Member 0's state as member k holds it:
-    Lookahead rebased(const char *lo, size_t S, int k) const {
+    // A call with one sampler per member (gnn_mlp_group_train_sampled_each) has a second such range while it runs: the device
+    // index region, member 0's ring in [idx_lo, idx_lo + idx_S), member k's at + k * idx_S.  Only the index pointers follow it;
+    // idx_S == 0: no region, the rule above alone.  (Invalidated entries are moved too: operator== compares them.)
+    Lookahead rebased(const char *lo, size_t S, int k, const char *idx_lo = nullptr, size_t idx_S = 0) const {
         auto moved = [&](auto *p) {
             const bool own = p && (size_t)(reinterpret_cast<const char *>(p) - lo) < S;
             return own ? reinterpret_cast<decltype(p)>(reinterpret_cast<const char *>(p) + (size_t)k * S) : p;
         };
+        auto moved_idx = [&](const int32_t *p) {
+            const bool ring = p && (size_t)(reinterpret_cast<uintptr_t>(p) - reinterpret_cast<uintptr_t>(idx_lo)) < idx_S;
+            return ring ? reinterpret_cast<const int32_t *>(reinterpret_cast<const char *>(p) + (size_t)k * idx_S) : moved(p);
+        };
         Lookahead r = *this;
-        r.slab.a0 = moved(slab.a0); r.slab.idx = moved(slab.idx); r.next.a0 = moved(next.a0); r.next.idx = moved(next.idx);
+        r.slab.a0 = moved(slab.a0); r.slab.idx = moved_idx(slab.idx); r.next.a0 = moved(next.a0); r.next.idx = moved_idx(next.idx);
         return r;
     }
+    // the device index region of such a call is released: as rows_renamed, and no entry keeps an address inside it (a later
+    // comparison between members, enter_grouped, knows of no region any more)
+    void index_region_released() { rows_renamed(); slab.idx = nullptr; next.idx = nullptr; }
     bool operator==(const Lookahead &o) const {
         return slab_valid == o.slab_valid && have_next == o.have_next && xstage_valid == o.xstage_valid && slab == o.slab && next == o.next && xstage_cur == o.xstage_cur;
     }

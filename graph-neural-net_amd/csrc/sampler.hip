@@ -2,12 +2,9 @@
 // refillSampler on java.util.Random, and gnn_mlp_train_sampled, the train loop of NNT:60-92 on a resident dataset.
 #include "handle.h"
 #include "java_random.h"
+#include "sample_ring.h"
 
 #include <algorithm>
-#include <chrono>
-#include <condition_variable>
-#include <mutex>
-#include <thread>
 
 using namespace gnn;
 using namespace gnn::host;
@@ -152,10 +149,13 @@ void gnn::host::sampler_assign(gnn_sampler_t *dst, const gnn_sampler_t *src) { *
 
 // `obs` (handle.h: SampledObserver) is called behind every step and behind every sampler chunk, on the calling thread, with the
 // handle's stream holding everything enqueued so far: the observed loops below and the group's (group.hip) are this loop + one.
-static int train_sampled_impl(gnn_mlp_t *h, gnn_sampler_t *s, int iterations, int batch, double step, double momentum,
-                              int noise, SampledObserver *obs) {
+// n samplers (n > 1: `each`, a group call with one sampler per member on member 0's handle): sampler m draws into ring m, and an
+// iteration whose n batch sizes differ is handed to each->mixed_step instead of being stepped here.
+static int train_sampled_impl(gnn_mlp_t *h, gnn_sampler_t *const *samplers, int n, int iterations, int batch, double step,
+                              double momentum, int noise, SampledObserver *obs, SampledEach *each) {
     TRY(check_handle(h));
-    TRY(train_sampled_checks(h, s, iterations, batch, step, noise));
+    if (n < 1 || n > GROUP_MAX || (n > 1 && !each)) return fail(GNN_ERR_BAD_ARG, "bad sampler count");
+    for (int m = 0; m < n; m++) TRY(train_sampled_checks(h, samplers[m], iterations, batch, step, noise));
     if (iterations >= 64) try_specialize(h);
     // The exact epoch sampler is serial host work (~10 us per batch of 128: two Fenwick walks per
     // draw) of the same order as a step on the GPU, so it runs AHEAD on a worker thread, chunk by
@@ -165,16 +165,20 @@ static int train_sampled_impl(gnn_mlp_t *h, gnn_sampler_t *s, int iterations, in
     // Index storage is a RING of kRing chunk slots on the host and on the device, whatever the run length (NNT:62 runs
     // 500 000 iterations): the sampler waits for a free host slot; a device slot is rewritten by a copy that is enqueued on
     // the handle's stream behind the steps that read it.
+    // With n samplers there are n such rings, slice m of ONE pinned and ONE device allocation (the device one is the index
+    // region of group_kernels.h), drawn by min(n, 8) worker threads (sample_ring.h: a grouped step of 8 nets takes 37 us, eight
+    // samplers on one thread 80).  The chunks are then shortened so that the n rings together stay within kPinnedBound.
     static constexpr int kRing = 4, kChunk = 256;
-    auto chunk_begin = [](int c) { // 0, 16, 48, 112, 240, 496, 752, ..
-        int b = 0, sz = 16;
-        for (int i = 0; i < c; i++) { b += sz; sz = std::min(kChunk, sz * 2); if (sz == kChunk && i + 1 < c) { b += (c - i - 1) * kChunk; break; } }
-        return b;
-    };
-    int n_chunks = 0;
-    while (chunk_begin(n_chunks) < iterations) n_chunks++;
-    auto chunk_end = [&](int c) { return std::min(iterations, chunk_begin(c + 1)); };
-    const size_t slot_elems = (size_t)kChunk * batch;
+    static constexpr size_t kPinnedBound = (size_t)64 << 20;
+    int kc = kChunk;
+    if (n > 1) while (kc > 1 && (size_t)n * kRing * kc * batch * sizeof(int32_t) > kPinnedBound) kc /= 2;
+    const ChunkSchedule sched{iterations, kc};
+    auto chunk_begin = [&](int c) { return sched.begin(c); };
+    auto chunk_end = [&](int c) { return sched.end(c); };
+    const int n_chunks = sched.chunks();
+    const size_t slot_elems = (size_t)kc * batch;
+    const size_t slice_elems = (slot_elems * kRing + 63) / 64 * 64; // (a slice starts on a 256-byte boundary)
+    const size_t cnt_slice = (size_t)kc * kRing;
     // The host ring is PINNED memory and every upload is followed by an event: the copy is then truly asynchronous (from pageable
     // memory hipMemcpyAsync stages the data before it returns -- in this runtime by waiting for the stream, i.e. for every step
     // queued so far: the GPU idled at each chunk boundary, and the slot's safety rested on that behaviour), and a host slot goes
@@ -183,59 +187,42 @@ static int train_sampled_impl(gnn_mlp_t *h, gnn_sampler_t *s, int iterations, in
         int32_t *p = nullptr; hipEvent_t ev[kRing] = {};
         ~PinnedRing() { if (p) (void)hipHostFree(p); for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
     } ring;
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&ring.p), slot_elems * kRing * sizeof(int32_t), hipHostMallocDefault));
+    HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&ring.p), slice_elems * n * sizeof(int32_t), hipHostMallocDefault));
     for (int i = 0; i < kRing; i++) HIP_TRY(hipEventCreateWithFlags(&ring.ev[i], hipEventDisableTiming));
     int32_t *const idx = ring.p;
-    std::vector<int> cnt((size_t)kChunk * kRing);
-    struct Shared {
-        std::mutex mu;
-        std::condition_variable cv;
-        int ready = 0, consumed = 0, sampler_rc = GNN_OK; // chunks sampled / chunks whose host slot is free again
-        bool stop = false;
-        std::string sampler_msg;
-    } sh;
-    std::thread producer([&]() {
-        for (int c = 0; c < n_chunks; c++) {
-            {
-                std::unique_lock<std::mutex> lk(sh.mu);
-                sh.cv.wait(lk, [&] { return sh.stop || c < sh.consumed + kRing; });
-                if (sh.stop) return;
-            }
-            int rc = GNN_OK;
-            const int i0 = chunk_begin(c), i1 = chunk_end(c);
-            int32_t *slot = idx + (size_t)(c % kRing) * slot_elems;
-            int *scnt = cnt.data() + (size_t)(c % kRing) * kChunk;
-            for (int i = i0; i < i1 && rc == GNN_OK; i++) rc = gnn_sampler_sample(s, batch, slot + (size_t)(i - i0) * batch, &scnt[i - i0]);
-            std::lock_guard<std::mutex> lk(sh.mu);
-            if (rc != GNN_OK) { sh.sampler_rc = rc; sh.sampler_msg = gnn_mlp_last_error(); sh.ready = n_chunks; sh.cv.notify_all(); return; }
-            sh.ready = c + 1;
-            sh.cv.notify_all();
-        }
-    });
-    struct Joiner { // the worker is joined on EVERY exit path, an exception included (a joinable std::thread's destructor terminates)
-        std::thread &t; Shared &sh;
-        ~Joiner() {
-            { std::lock_guard<std::mutex> lk(sh.mu); sh.stop = true; }
-            sh.cv.notify_all();
-            if (t.joinable()) t.join();
-        }
-    } joiner{producer, sh};
-    std::vector<int> dcnt((size_t)kRing * kChunk, 0); // the batch sizes of the chunks on the device (the host ring is the sampler's again by then)
+    std::vector<int> cnt(cnt_slice * n);
+    std::vector<int> dcnt(cnt_slice * n, 0); // the batch sizes of the chunks on the device (the host ring is the sampler's again by then)
     DevScratch dbuf;
-    int rc = dbuf.alloc(slot_elems * kRing * sizeof(int32_t));
+    TRY(dbuf.alloc(slice_elems * n * sizeof(int32_t)));
     int32_t *d_idx = dbuf.as<int32_t>();
+    SampleRing sr(n, kRing, n_chunks);
+    // (declared behind everything the workers write: they are joined first on every exit path)
+    SampleWorkers workers(sr, SampleWorkers::threads_for(n), [&](int m, int c, std::string *msg) -> int {
+        int rc = GNN_OK;
+        const int i0 = chunk_begin(c), i1 = chunk_end(c);
+        int32_t *slot = idx + (size_t)m * slice_elems + (size_t)(c % kRing) * slot_elems;
+        int *scnt = cnt.data() + (size_t)m * cnt_slice + (size_t)(c % kRing) * kc;
+        for (int i = i0; i < i1 && rc == GNN_OK; i++) rc = gnn_sampler_sample(samplers[m], batch, slot + (size_t)(i - i0) * batch, &scnt[i - i0]);
+        if (rc != GNN_OK) *msg = gnn_mlp_last_error();
+        return rc;
+    });
+    if (each) each->region(d_idx, slice_elems * sizeof(int32_t));
+    int rc = GNN_OK;
     // Chunk c + 1's draws go to the device ring BEFORE chunk c's steps are enqueued (when the sampler has them, which it has:
     // it runs kRing chunks ahead): the last step of a chunk then knows its successor like every other step, and the chain of
     // two-launch steps runs through the chunk boundary -- an upload in stream order at the boundary left the GPU idle for
     // the copy and restarted the chain with a forward-only launch, ~1 us per step over a run.
     int uploaded = 0; // chunks whose draws are on the device (or in flight in front of every launch that reads them)
     int released = 0; // chunks whose HOST slot is the sampler's again (their upload's event has completed)
-    auto upload = [&](int c) -> int {
+    auto upload = [&](int c) -> int { // (every member's part: one copy per ring, one event behind them)
         const int j0 = chunk_begin(c), j1 = chunk_end(c);
-        const size_t so = (size_t)(c % kRing) * slot_elems;
-        // (the counts are copied out of the ring at once; the indices stay in the pinned slot until the copy has run)
-        std::copy(cnt.begin() + (size_t)(c % kRing) * kChunk, cnt.begin() + (size_t)(c % kRing) * kChunk + (j1 - j0), dcnt.begin() + (size_t)(c % kRing) * kChunk);
-        hipError_t e = hipMemcpyAsync(d_idx + so, idx + so, (size_t)(j1 - j0) * batch * sizeof(int32_t), hipMemcpyHostToDevice, h->stream);
+        hipError_t e = hipSuccess;
+        for (int m = 0; m < n && e == hipSuccess; m++) {
+            const size_t so = (size_t)m * slice_elems + (size_t)(c % kRing) * slot_elems, co = (size_t)m * cnt_slice + (size_t)(c % kRing) * kc;
+            // (the counts are copied out of the ring at once; the indices stay in the pinned slot until the copy has run)
+            std::copy(cnt.begin() + co, cnt.begin() + co + (j1 - j0), dcnt.begin() + co);
+            e = hipMemcpyAsync(d_idx + so, idx + so, (size_t)(j1 - j0) * batch * sizeof(int32_t), hipMemcpyHostToDevice, h->stream);
+        }
         if (e == hipSuccess) e = hipEventRecord(ring.ev[c % kRing], h->stream);
         if (e != hipSuccess) return fail(GNN_ERR_HIP, std::string("hipMemcpyAsync: ") + hipGetErrorString(e));
         uploaded = c + 1;
@@ -252,48 +239,52 @@ static int train_sampled_impl(gnn_mlp_t *h, gnn_sampler_t *s, int iterations, in
             if (q != hipSuccess) return fail(GNN_ERR_HIP, std::string("upload event: ") + hipGetErrorString(q));
             r++;
         }
-        if (r != released) {
-            released = r;
-            { std::lock_guard<std::mutex> lk(sh.mu); sh.consumed = r; }
-            sh.cv.notify_all();
-        }
+        if (r != released) { released = r; sr.release(r); }
         return GNN_OK;
     };
+    // the n batch sizes of the iteration at `at` of chunk slot `slot` (on the device): member 0's when they agree, else -1
+    auto common_count = [&](int slot, int at) {
+        const int c0 = dcnt[(size_t)slot * kc + at];
+        for (int m = 1; m < n; m++) if (dcnt[(size_t)m * cnt_slice + (size_t)slot * kc + at] != c0) return -1;
+        return c0;
+    };
+    int member_cnt[GROUP_MAX];
     for (int c = 0; c < n_chunks && rc == GNN_OK; c++) {
         rc = release(false);
         if (rc != GNN_OK) break;
         if (uploaded <= c) {
-            std::unique_lock<std::mutex> lk(sh.mu);
             // (the sampler may be waiting for a host slot whose upload is still in flight: hand slots back while waiting for it)
-            while (!(sh.ready > c)) {
-                lk.unlock();
+            while (!sr.ready(c)) {
                 rc = release(uploaded - released >= kRing); // every slot taken and none released: wait for the oldest upload
-                lk.lock();
-                if (rc != GNN_OK || sh.ready > c) break;
-                sh.cv.wait_for(lk, std::chrono::microseconds(200));
+                if (rc != GNN_OK || sr.wait_ready(c, 200)) break;
             }
             if (rc != GNN_OK) break;
-            if (sh.sampler_rc != GNN_OK) { rc = fail(sh.sampler_rc, sh.sampler_msg); break; }
-            lk.unlock();
+            std::string msg;
+            if (const int src = sr.error(&msg)) { rc = fail(src, msg); break; }
             rc = upload(c);
             if (rc != GNN_OK) break;
         }
         if (c + 1 < n_chunks) { // the successor too, if it is drawn already (no waiting for it)
-            bool have = false;
-            { std::lock_guard<std::mutex> lk(sh.mu); have = sh.ready > c + 1 && sh.sampler_rc == GNN_OK; }
-            if (have) { rc = upload(c + 1); if (rc != GNN_OK) break; }
+            if (sr.ready(c + 1) && sr.error() == GNN_OK) { rc = upload(c + 1); if (rc != GNN_OK) break; }
         }
         const int i0 = chunk_begin(c), i1 = chunk_end(c);
-        const size_t so = (size_t)(c % kRing) * slot_elems;
-        const int *ccnt = dcnt.data() + (size_t)(c % kRing) * kChunk;
+        const int slot = c % kRing, slot_n = (c + 1) % kRing;
+        const size_t so = (size_t)slot * slot_elems, sn = (size_t)slot_n * slot_elems;
         for (int i = i0; i < i1 && rc == GNN_OK; i++) {
-            if (h->chain && i + 1 < i1) { // the next draw of this chunk is already on the device
-                h->la.announce(NextBatch{h->DX, d_idx + so + (size_t)(i + 1 - i0) * batch, ccnt[i + 1 - i0]});
-            } else if (h->chain && uploaded > c + 1) { // ... and so is the first draw of the next chunk
-                const size_t sn = (size_t)((c + 1) % kRing) * slot_elems;
-                h->la.announce(NextBatch{h->DX, d_idx + sn, dcnt[(size_t)((c + 1) % kRing) * kChunk]});
+            const int B = common_count(slot, i - i0);
+            if (B < 0) { // the members' batches differ in size (a refill shortened some): member after member, nothing announced
+                for (int m = 0; m < n; m++) member_cnt[m] = dcnt[(size_t)m * cnt_slice + (size_t)slot * kc + (i - i0)];
+                rc = each->mixed_step(d_idx + so + (size_t)(i - i0) * batch, member_cnt);
+            } else {
+                if (h->chain && i + 1 < i1) { // the next draw of this chunk is already on the device
+                    const int Bn = common_count(slot, i + 1 - i0);
+                    if (Bn >= 0) h->la.announce(NextBatch{h->DX, d_idx + so + (size_t)(i + 1 - i0) * batch, Bn});
+                } else if (h->chain && uploaded > c + 1) { // ... and so is the first draw of the next chunk
+                    const int Bn = common_count(slot_n, 0);
+                    if (Bn >= 0) h->la.announce(NextBatch{h->DX, d_idx + sn, Bn});
+                }
+                rc = step_on_device_indices(h, d_idx + so + (size_t)(i - i0) * batch, B, step, momentum);
             }
-            rc = step_on_device_indices(h, d_idx + so + (size_t)(i - i0) * batch, ccnt[i - i0], step, momentum);
             // (a validation pass reads the weights the step has just written; it touches neither the slabs the step's tile
             //  kernel made for the next batch nor the staged rows, so the chain of two-launch steps runs on behind it)
             if (rc == GNN_OK && obs) rc = obs->after_step(i);
@@ -303,12 +294,17 @@ static int train_sampled_impl(gnn_mlp_t *h, gnn_sampler_t *s, int iterations, in
     // (on an early exit the sampler stops after the chunk it is drawing: its state stays well defined)
     (void)hipStreamSynchronize(h->stream); // the device ring is released below
     h->la.rows_renamed(); // (they may name rows through d_idx)
+    if (each) each->region(nullptr, 0);
     return rc;
 }
 
 int gnn::host::train_sampled_run(gnn_mlp *h, gnn_sampler_t *s, int iterations, int batch, double step, double momentum, int noise,
                                  SampledObserver *obs) {
-    return train_sampled_impl(h, s, iterations, batch, step, momentum, noise, obs);
+    return train_sampled_impl(h, &s, 1, iterations, batch, step, momentum, noise, obs, nullptr);
+}
+int gnn::host::train_sampled_run_each(gnn_mlp *h, gnn_sampler_t *const *samplers, int n, int iterations, int batch, double step,
+                                      double momentum, int noise, SampledObserver *obs, SampledEach *each) {
+    return train_sampled_impl(h, samplers, n, iterations, batch, step, momentum, noise, obs, each);
 }
 
 namespace {
@@ -331,7 +327,7 @@ extern "C" {
 
 int gnn_mlp_train_sampled(gnn_mlp_t *h, gnn_sampler_t *s, int iterations, int batch, double step, double momentum,
                           int noise) { return guarded([&]() -> int {
-    return train_sampled_impl(h, s, iterations, batch, step, momentum, noise, nullptr);
+    return train_sampled_impl(h, &s, 1, iterations, batch, step, momentum, noise, nullptr, nullptr);
 }); }
 
 int gnn_mlp_train_sampled_observed(gnn_mlp_t *h, gnn_sampler_t *s, int iterations, int batch, double step, double momentum,
@@ -348,7 +344,7 @@ int gnn_mlp_train_sampled_observed(gnn_mlp_t *h, gnn_sampler_t *s, int iteration
     const bool rows_form = eval_block_rows(h, validation_size) >= validation_size && (int64_t)iterations * stride * 4 <= (1ll << 30);
     if (rows_form) TRY(drows.alloc(sizeof(float) * (size_t)iterations * (size_t)stride));
     LoneValidation obs(h, validation_size, dv.as<double>(), rows_form ? drows.as<float>() : nullptr, stride);
-    TRY(train_sampled_impl(h, s, iterations, batch, step, momentum, noise, &obs));
+    TRY(train_sampled_impl(h, &s, 1, iterations, batch, step, momentum, noise, &obs, nullptr));
     if (rows_form) {
         hipLaunchKernelGGL(sum_rows_kernel, dim3(iterations), dim3(256), 0, h->stream, RowSumParams{drows.as<float>(), stride, validation_size, dv.as<double>()});
         TRY_LAUNCHES(h);

@@ -488,25 +488,54 @@ class NetGroup:
         st, mo = _per_member("steps", steps, len(self)), _per_member("momenta", momenta, len(self))
         _capi.check(self._lib.gnn_mlp_group_train_range(self._h, int(first), int(B), int(n_steps), _dp(st), _dp(mo)))
 
+    def _samplers(self, sampler):
+        """None for ONE sampler (anything with a handle); for a sequence of K samplers, one per member, the handle array."""
+        if hasattr(sampler, "_h"):
+            return None
+        ss = list(sampler)
+        if len(ss) != len(self):
+            raise ValueError("samplers: one per member (%d), got %d" % (len(self), len(ss)))
+        return (C.c_void_p * len(ss))(*[s._h for s in ss])
+
     def train_sampled(self, sampler, iterations, batch, steps, momenta, noise=False):
-        """NNT:82-90 for every member with the draws of ONE sampler (trainer.Sampler)."""
+        """NNT:82-90 for every member: with the draws of ONE sampler (trainer.Sampler), or, given a sequence of K samplers,
+        member k with the draws of sampler[k] -- K independent NeuralNetTrainer runs (gnn_mlp_group_train_sampled_each)."""
         st, mo = _per_member("steps", steps, len(self)), _per_member("momenta", momenta, len(self))
+        each = self._samplers(sampler)
+        if each is not None:
+            _capi.check(self._lib.gnn_mlp_group_train_sampled_each(self._h, each, int(iterations), int(batch), _dp(st), _dp(mo),
+                                                                   int(bool(noise)), 0, None))
+            return
         _capi.check(self._lib.gnn_mlp_group_train_sampled(self._h, sampler._h, int(iterations), int(batch), _dp(st), _dp(mo),
                                                           int(bool(noise))))
 
     def train_sampled_observed(self, sampler, iterations, batch, steps, momenta, validation_size=None, noise=False):
-        """NNT:68-72 / 75-79 for every member with the draws of ONE sampler: train_sampled, and after every iteration
-        validate(validation_size) (NNT:102-113, the mean loss of the first rows of the data set; default rows // 100 + 1,
-        NNT:65) of every member.  Returns the curves, an ndarray (iterations, K), from one readback."""
+        """NNT:68-72 / 75-79 for every member with the draws of ONE sampler, or of one sampler per member (a sequence of K):
+        train_sampled, and after every iteration validate(validation_size) (NNT:102-113, the mean loss of the first rows of the
+        data set; default rows // 100 + 1, NNT:65) of every member.  Returns the curves, an ndarray (iterations, K), from one
+        readback."""
         st, mo = _per_member("steps", steps, len(self)), _per_member("momenta", momenta, len(self))
+        each = self._samplers(sampler)
         if validation_size is None:
             if getattr(self, "_dataset_rows", None) is None:
                 raise ValueError("validation_size=None needs an uploaded data set")
             validation_size = self._dataset_rows // 100 + 1
         val = np.empty((max(int(iterations), 0), len(self)), dtype=np.float64)
+        if each is not None:
+            _capi.check(self._lib.gnn_mlp_group_train_sampled_each(self._h, each, int(iterations), int(batch), _dp(st), _dp(mo),
+                                                                   int(bool(noise)), int(validation_size), _dp(val)))
+            return val
         _capi.check(self._lib.gnn_mlp_group_train_sampled_observed(self._h, sampler._h, int(iterations), int(batch), _dp(st), _dp(mo),
                                                                    int(bool(noise)), int(validation_size), _dp(val)))
         return val
+
+    @property
+    def sampled_each_iterations(self):
+        """(grouped, member_after_member) of the last call with one sampler per member: iterations stepped by the grouped
+        launches / member after member (batch sizes that differed at a refill, or a group without grouped launches)."""
+        a, b = C.c_int64(), C.c_int64()
+        _capi.check(self._lib.gnn_mlp_group_sampled_each_iterations(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     @property
     def observed_launches(self):

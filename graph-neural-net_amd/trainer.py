@@ -118,7 +118,8 @@ class NeuralNetTrainer:
 
 class NetGroupTrainer:
     """NeuralNetTrainer for a NetGroup: ONE data set and ONE sampler (Random(seed), NNT:42) for every member -- the reference's
-    sweep of MNISTTrainer runs, each of which samples with Random(1), as one trainer."""
+    sweep of MNISTTrainer runs, each of which samples with Random(1), as one trainer.  seed: a sequence of K seeds gives
+    member k its own sampler Random(seed[k]) -- K independent runs, the sampler's share of a seed-variance study included."""
 
     OBSERVER_BURST = NeuralNetTrainer.OBSERVER_BURST
 
@@ -129,7 +130,12 @@ class NetGroupTrainer:
         else:
             group.upload_dataset(data_x, data_y)
         self.size = group._dataset_rows
-        self.sampler = Sampler(self.size, seed)
+        if np.ndim(seed) == 0:
+            self.sampler = Sampler(self.size, seed)
+        else:
+            if len(seed) != len(group):
+                raise ValueError("seed: one per member (%d), got %d" % (len(group), len(seed)))
+            self.sampler = [Sampler(self.size, s) for s in seed]
 
     def train(self, iterations, stepSizes, batchSize, momenta, noise=False, monitor=None, observers=None):
         """NNT:60-92 for every member (stepSizes / momenta: one value per member, or a scalar for all).  observers: K text

@@ -340,6 +340,22 @@ int gnn_mlp_group_train_sampled_observed(gnn_mlp_group_t *g, gnn_sampler_t *s, i
  * on the device; 0: member after member, each through gnn_mlp_train_sampled_observed on its own handle (groups of one net, or
  * without grouped step launches) -- column k is then bit for bit the lone handle's curve */
 int gnn_mlp_group_observed_launches(const gnn_mlp_group_t *g);
+/* gnn_mlp_group_train_sampled / _observed with ONE SAMPLER PER MEMBER: member k ends bit for bit (weights, momentum, time)
+ * where the lone handle created with seeds[k] ends after gnn_mlp_train_sampled(samplers[k], iterations, batch, steps[k],
+ * momenta[k]); samplers[k] ends where it ends there.  val_loss null: unobserved (validation_size ignored); else
+ * val_loss[i * K + k] = validate(validation_size) of member k after iteration i, as gnn_mlp_group_train_sampled_observed.
+ * The samplers may be in any state and are independent of one another; their draws are made on up to 8 worker threads.
+ * An iteration in which every member's batch has the same size -- every full batch -- is stepped by the two grouped launches;
+ * a refill shortens a batch per member (NNT:149-155), and an iteration whose sizes differ is stepped member after member.
+ * Refused before any step and any draw: a null or repeated sampler, a sampler whose size differs from the data set, batch not
+ * below it (NNT:63), val_loss with validation_size outside [1, rows] -> GNN_ERR_BAD_ARG; noise != 0 -> GNN_ERR_UNSUPPORTED.
+ * Groups without grouped launches (gnn_mlp_group_launches_per_step() == 0, one member; observed: gnn_mlp_group_observed_launches()
+ * == 0) run member k through gnn_mlp_train_sampled(_observed) with samplers[k]. */
+int gnn_mlp_group_train_sampled_each(gnn_mlp_group_t *g, gnn_sampler_t *const *samplers, int iterations, int batch,
+                                     const double *steps, const double *momenta, int noise,
+                                     int validation_size, double *val_loss);
+/* of the LAST gnn_mlp_group_train_sampled_each call: iterations stepped by grouped launches / member after member */
+int gnn_mlp_group_sampled_each_iterations(const gnn_mlp_group_t *g, int64_t *grouped, int64_t *member_after_member);
 int gnn_mlp_group_synchronize(gnn_mlp_group_t *g);
 /* Evaluation of a whole group in one pass (csrc/group_eval_kernel.h).
  * 2: one grouped forward launch + one combine launch per block of rows; 0: member after member */
