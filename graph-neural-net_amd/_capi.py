@@ -91,6 +91,7 @@ SYMBOLS = [
     ("gnn_mlp_group_train_sampled_observed", C.c_int, [_H, _H, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp]),
     ("gnn_mlp_group_observed_launches", C.c_int, [_H]),
     ("gnn_mlp_group_train_sampled_each", C.c_int, [_H, C.POINTER(_H), C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp]),
+    ("gnn_mlp_group_train_sampled_sizes", C.c_int, [_H, C.POINTER(_H), C.c_int, _ip, _dp, _dp, C.c_int, C.c_int, _dp]),
     ("gnn_mlp_group_sampled_each_iterations", C.c_int, [_H, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     ("gnn_mlp_group_synchronize", C.c_int, [_H]),
     ("gnn_mlp_group_eval_launches", C.c_int, [_H]),

@@ -7,7 +7,8 @@
 // launch_small.hip) with GroupLaunch set, which turns each of its two launches into the grouped launch -- there is no second
 // copy of the chain logic.  What a step reads and every member shares -- the dataset, the device index ring of a sampled
 // call -- is member 0's and lies outside the arena.  (A call with one sampler per member keeps K index rings in one region
-// outside the arena, a second relocatable range: the end of this file.)  Nets off the two-launch path are stepped one member
+// outside the arena, a second relocatable range; a call with one BATCH SIZE per member, gnn_mlp_group_train_sampled_sizes, hands
+// the grouped launches every member's own row count: the end of this file.)  Nets off the two-launch path are stepped one member
 // after another through their own handles: the same results, no speed-up.
 #include "handle.h"
 
@@ -28,23 +29,32 @@ void free_group(gnn_mlp_group *g) {
     delete g;
 }
 
+static_assert(kGroupSizesMax == GROUP_MAX, "group_sizes.h and group_kernels.h: one member count");
+
 // Before a grouped call: every member's deferred update is applied, and member 0's look-ahead state (lookahead.h) -- which the
-// grouped launches act on for everyone -- must describe every member.  If it does not (a member was stepped alone), all of it
-// is dropped: forgetting keeps results bitwise, it only costs a forward-only launch.
+// grouped launches act on for everyone -- must describe every member: member k holds it with its own pointers and, after a call
+// with one batch size per member, its own sizes (group_sizes.h: the group's record of them).  If it does not (a member was
+// stepped alone), all of it is dropped: forgetting keeps results bitwise, it only costs a forward-only launch.
 int enter_grouped(gnn_mlp_group *g) {
     for (gnn_mlp *h : g->m) TRY(check_handle(h));
-    bool same = true;
-    for (int k = 1; k < g->K && same; k++) same = g->m[0]->la.rebased(g->arena, g->S, k) == g->m[k]->la;
+    const Lookahead &l0 = g->m[0]->la;
+    // (sizes that differ between the members describe batches of a sized call's index region, which is gone: never live)
+    bool same = g->sizes.describes(l0) && (g->sizes.is_uniform(g->K) || (!l0.slab_valid && !l0.have_next));
+    for (int k = 1; k < g->K && same; k++) same = g->sizes.member_view(l0, g->arena, g->S, k) == g->m[k]->la;
     if (!same)
         for (int k = 0; k < g->K; k++) { g->m[k]->la = g->m[0]->la.rebased(g->arena, g->S, k); g->m[k]->la.forget(); } // (one staging buffer index for all)
+    if (!same) g->sizes.uniform(g->K, g->m[0]->la);
     return GNN_OK;
 }
 // After it: member 0's step count and look-ahead state, moved to each member.  (idx_lo, idx_S: the index region of a call
-// with one sampler per member while it is live -- lookahead.h.)
-void leave_grouped(gnn_mlp_group *g, int steps_done, const char *idx_lo = nullptr, size_t idx_S = 0) {
+// with one sampler per member while it is live -- lookahead.h.  sizes: the members' own batch sizes, a sized call; else member
+// 0's hold for all.)
+void leave_grouped(gnn_mlp_group *g, int steps_done, const char *idx_lo = nullptr, size_t idx_S = 0, const GroupSizes *sizes = nullptr) {
+    if (sizes) g->sizes = *sizes;
+    else g->sizes.uniform(g->K, g->m[0]->la);
     for (int k = 1; k < g->K; k++) {
         g->m[k]->time += steps_done;
-        g->m[k]->la = g->m[0]->la.rebased(g->arena, g->S, k, idx_lo, idx_S);
+        g->m[k]->la = g->sizes.member_view(g->m[0]->la, g->arena, g->S, k, idx_lo, idx_S);
     }
 }
 
@@ -59,6 +69,7 @@ int group_launch(const gnn_mlp_group *g, const double *steps, const double *mome
     gl->arena_lo = g->arena;
     gl->S = g->S;
     gl->rb_fn = g->rb_fn;
+    gl->rb_fn_sized = g->rb_fn_sized;
     for (int k = 0; k < g->K; k++) { gl->step[k] = steps[k]; gl->momentum[k] = momenta[k]; }
     return GNN_OK;
 }
@@ -120,7 +131,13 @@ int gnn_mlp_group_create(const int32_t *dims, int n_dims, int out_kind, int inne
             (void)hipGetLastError();
             g->rb_fn = nullptr;
         }
-        g->grouped = g->rb_fn != nullptr;
+        // (the sized twin, for calls with one batch size per member: both or neither)
+        g->rb_fn_sized = g->rb_fn ? rb_group_sized_function(h0) : nullptr;
+        if (g->rb_fn_sized && hipFuncSetAttribute(g->rb_fn_sized, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h0->rb_lds_bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            g->rb_fn_sized = nullptr;
+        }
+        g->grouped = g->rb_fn != nullptr && g->rb_fn_sized != nullptr;
     }
     plan_group_eval(g.get());
     HIP_TRY(hipStreamSynchronize(g->stream));
@@ -381,11 +398,13 @@ int gnn_mlp_group_train_sampled_each(gnn_mlp_group_t *g, gnn_sampler_t *const *s
     TRY(group_launch(g, steps, momenta, &gl));
     EachMember each;
     each.g = g; each.gl = &gl; each.steps = steps; each.momenta = momenta;
+    int nominal[GROUP_MAX];
+    for (int k = 0; k < K; k++) nominal[k] = batch;
     const int t0 = h0->time;
     int rc;
     {
         GroupScope scope(h0, &gl);
-        rc = train_sampled_run_each(h0, samplers, K, iterations, batch, steps[0], momenta[0], noise, val_loss ? &obs : nullptr, &each);
+        rc = train_sampled_run_each(h0, samplers, K, iterations, nominal, steps[0], momenta[0], noise, val_loss ? &obs : nullptr, &each);
     }
     const int done = h0->time - t0;
     // (a mixed iteration advanced every member's step count through its own handle: only the grouped ones are member 0's alone)
@@ -395,6 +414,133 @@ int gnn_mlp_group_train_sampled_each(gnn_mlp_group_t *g, gnn_sampler_t *const *s
     if (val_loss) {
         HIP_TRY(hipMemcpy(val_loss, val.p, sizeof(double) * (size_t)iterations * K, hipMemcpyDeviceToHost));
         for (size_t i = 0; i < (size_t)iterations * K; i++) val_loss[i] /= (double)validation_size; // NNT:112
+    }
+    return GNN_OK;
+}); }
+
+} // extern "C"
+
+/* One batch size per member (the reference's recorded sweep, logs/trainLog.csv rows 1-3: three step sizes AND three batch sizes).
+ * The loop is the one above with ring m drawn at batches[m]; EVERY iteration is the two grouped launches, member k with its own
+ * live row count now and in the announced iteration (GroupLaunch::rows / next_rows, group_kernels.h) -- a refill that shortens
+ * one member's batch changes that member's entry, nothing else.  The per-iteration decision is group_sizes.h's. */
+namespace {
+struct SizedMembers : SampledEach {
+    gnn_mlp_group *g; GroupLaunch *gl;
+    GroupSizes track; // member k's sizes of the batches member 0's state names, step by step
+    ~SizedMembers() override { if (gl->idx_lo) region(nullptr, 0); } // (the loop was left by an exception)
+    void region(const int32_t *lo, size_t slice_bytes) override {
+        if (!lo) { // about to be released: no member keeps an address inside it
+            leave_grouped(g, 0, gl->idx_lo, gl->idx_S, &track);
+            for (gnn_mlp *h : g->m) h->la.index_region_released();
+        }
+        gl->idx_lo = reinterpret_cast<const char *>(lo); gl->idx_S = slice_bytes;
+    }
+    int mixed_step(const int32_t *, const int *) override { return fail(GNN_ERR_STATE, "a sized group call steps no iteration member after member"); }
+    bool sized() const override { return true; }
+    void step_sizes(const int *rows, const int *next_rows) override {
+        const SizedStep s = make_sized_step(g->K, rows, next_rows);
+        for (int k = 0; k < g->K; k++) { gl->rows[k] = s.rows[k]; gl->next_rows[k] = s.next_rows[k]; }
+        gl->next_same_rows = s.next_same_rows;
+        track.stepped(g->K, s);
+    }
+};
+// The observed form of a sized call.  Column k is the lone handle's curve BIT FOR BIT, as the members are the lone nets: the
+// grouped validation kernel (group_eval.hip) forms the per-row losses in another order than the single-net forward kernels and
+// differs from them in the last bits (2e-7 relative on the curves of tests/test_group_batches_gpu.py), so behind every grouped
+// step each member's validation pass is the lone one (sampler.hip), through its own handle on the group's stream -- the forward
+// kernels read the weights the step has just written and touch neither slabs nor staged rows.  Sums to val[k][i]: the per-row
+// losses kept in rows[k][i][..] and summed by one launch behind the loop when that fits 1 GiB, else summed per iteration (the
+// same fp64 sum either way: eval_kernels.h).
+struct MemberValidation : SampledObserver {
+    gnn_mlp_group *g; int validation_size, iterations; int64_t stride;
+    float *d_rows; double *d_val;
+    int after_step(int i) override {
+        for (int k = 0; k < g->K; k++) {
+            gnn_mlp *h = g->m[(size_t)k];
+            const size_t at = (size_t)k * iterations + i;
+            int vrc = GNN_OK;
+            if (d_rows && validation_losses_to_row(h, validation_size, d_rows + at * stride, &vrc)) { TRY(vrc); continue; }
+            TRY(validation_loss_sum(h, validation_size, d_val + at));
+        }
+        return GNN_OK;
+    }
+    int after_chunk(int) override {
+        for (gnn_mlp *h : g->m) TRY_LAUNCHES(h);
+        return GNN_OK;
+    }
+};
+} // namespace
+
+extern "C" {
+
+int gnn_mlp_group_train_sampled_sizes(gnn_mlp_group_t *g, gnn_sampler_t *const *samplers, int iterations, const int32_t *batches,
+                                      const double *steps, const double *momenta, int noise, int validation_size,
+                                      double *val_loss) { return guarded([&]() -> int {
+    TRY(check_group(g));
+    TRY(check_per_member(g, steps, momenta));
+    const int K = g->K;
+    gnn_mlp *h0 = g->m[0];
+    if (!samplers) return fail(GNN_ERR_BAD_ARG, "samplers is null");
+    if (!batches) return fail(GNN_ERR_BAD_ARG, "batches is null: one batch size per member");
+    for (int k = 0; k < K; k++) if (!samplers[k]) return fail(GNN_ERR_BAD_ARG, "null sampler");
+    for (int k = 0; k < K; k++)
+        for (int j = 0; j < k; j++)
+            if (samplers[j] == samplers[k]) return fail(GNN_ERR_BAD_ARG, "the same sampler for two members: every member draws from its own");
+    for (int k = 0; k < K; k++) TRY(train_sampled_checks(g->m[k], samplers[k], iterations, batches[k], steps[k], noise));
+    if (val_loss && (validation_size <= 0 || validation_size > h0->dataset_n)) return fail(GNN_ERR_BAD_ARG, "validation size outside the dataset (NNT:104)");
+    g->each_grouped = g->each_mixed = 0;
+    const bool fallback = K == 1 || !g->grouped || (val_loss && gnn_mlp_group_observed_launches(g) != 3);
+    if (fallback) { // member after member, each with its own sampler and batch size through its own handle
+        std::vector<double> col(val_loss ? (size_t)iterations : 0);
+        for (int k = 0; k < K; k++) {
+            if (!val_loss) { TRY(gnn_mlp_train_sampled(g->m[(size_t)k], samplers[k], iterations, batches[k], steps[k], momenta[k], noise)); continue; }
+            TRY(gnn_mlp_train_sampled_observed(g->m[(size_t)k], samplers[k], iterations, batches[k], steps[k], momenta[k], noise, validation_size, col.data()));
+            for (int i = 0; i < iterations; i++) val_loss[(size_t)i * K + k] = col[(size_t)i];
+        }
+        g->each_mixed = iterations;
+        return GNN_OK;
+    }
+    MemberValidation obs;
+    DevScratch rows, val;
+    bool rows_form = false;
+    if (val_loss) {
+        obs.g = g; obs.validation_size = validation_size; obs.iterations = iterations; obs.stride = pad_up(validation_size);
+        rows_form = eval_block_rows(h0, validation_size) >= validation_size && (int64_t)K * iterations * obs.stride * 4 <= (1ll << 30);
+        if (rows_form) TRY(rows.alloc(sizeof(float) * (size_t)K * (size_t)iterations * (size_t)obs.stride));
+        TRY(val.alloc(sizeof(double) * (size_t)iterations * K));
+        obs.d_rows = rows_form ? rows.as<float>() : nullptr; obs.d_val = val.as<double>();
+    }
+    TRY(enter_grouped(g));
+    GroupLaunch gl;
+    TRY(group_launch(g, steps, momenta, &gl));
+    gl.sized = true;
+    SizedMembers each;
+    each.g = g; each.gl = &gl; each.track = g->sizes;
+    int nominal[GROUP_MAX];
+    for (int k = 0; k < K; k++) nominal[k] = batches[k];
+    const int t0 = h0->time;
+    int rc;
+    {
+        GroupScope scope(h0, &gl);
+        rc = train_sampled_run_each(h0, samplers, K, iterations, nominal, steps[0], momenta[0], noise, val_loss ? &obs : nullptr, &each);
+    }
+    const int done = h0->time - t0;
+    leave_grouped(g, done, nullptr, 0, &each.track);
+    g->each_grouped = done;
+    TRY(rc);
+    if (val_loss) {
+        if (rows_form) {
+            hipLaunchKernelGGL(sum_rows_kernel, dim3((unsigned)K * (unsigned)iterations), dim3(256), 0, h0->stream,
+                               RowSumParams{rows.as<float>(), obs.stride, validation_size, val.as<double>()});
+            TRY_LAUNCHES(h0);
+            HIP_TRY(hipStreamSynchronize(h0->stream));
+        }
+        // (the loop has waited for the stream: one readback of val[k][i], transposed on the host)
+        std::vector<double> col((size_t)iterations * K);
+        HIP_TRY(hipMemcpy(col.data(), val.p, sizeof(double) * col.size(), hipMemcpyDeviceToHost));
+        for (int k = 0; k < K; k++)
+            for (int i = 0; i < iterations; i++) val_loss[(size_t)i * K + k] = col[(size_t)k * iterations + i] / (double)validation_size; // NNT:112
     }
     return GNN_OK;
 }); }

@@ -15,6 +15,7 @@
 #include "kernels.h"
 #include "eval_kernels.h"
 #include "lookahead.h"
+#include "group_sizes.h"
 #include "timer_slots.h"
 
 #include <hip/hip_ext.h>
@@ -37,8 +38,17 @@ struct GroupLaunch {
     int K = 0;
     const char *arena_lo = nullptr; size_t S = 0;
     const void *rb_fn = nullptr; // the grouped row-block kernel of the net (rb_group_function)
+    const void *rb_fn_sized = nullptr; // ... and its sized twin (rb_group_sized_function)
     double step[GROUP_MAX] = {}, momentum[GROUP_MAX] = {};
     const char *idx_lo = nullptr; size_t idx_S = 0; // the device index region of a call with one sampler per member (else 0)
+    // One batch size per member (gnn_mlp_group_train_sampled_sizes): member k's live rows in the iteration being stepped and in
+    // the announced one, set by the loop before every step (group_sizes.h): the launches are the sized twins' (group_kernels.h).
+    // Not sized: member 0's counts hold for all.
+    bool sized = false;
+    int rows[GROUP_MAX] = {}, next_rows[GROUP_MAX] = {};
+    // what member 0's control path decides from "the announced batch has the current batch's size" (plan.hip: rb_next) must hold
+    // for EVERY member: false when it fails for one
+    bool next_same_rows = true;
 };
 } // namespace host
 } // namespace gnn
@@ -187,12 +197,14 @@ struct gnn_mlp_group {
     std::vector<gnn_mlp *> m;
     bool grouped = false;         // every launch of a step serves all members
     const void *rb_fn = nullptr;  // the grouped row-block kernel (rb_group_function)
+    const void *rb_fn_sized = nullptr; // its sized twin (rb_group_sized_function)
     // evaluation in grouped launches (group_eval_kernel.h): the plan made at create, and the workspace -- K x block rows x
     // (16 + 2) words, allocated on first use, grown on demand
     struct EvalPlan { bool ok = false; int mt = 0; gnn::GroupEvalLds lds{}; const void *fn = nullptr, *fn_loss = nullptr; } eval_plan; // (fn_loss: the LOSS_ONLY twin)
     float *eval_ws = nullptr;
     int eval_ws_rows = 0;
-    int64_t each_grouped = 0, each_mixed = 0; // of the last gnn_mlp_group_train_sampled_each call: iterations by grouped launches / member after member
+    int64_t each_grouped = 0, each_mixed = 0; // of the last gnn_mlp_group_train_sampled_each / _sizes call: iterations by grouped launches / member after member
+    gnn::host::GroupSizes sizes;  // member k's sizes of the batches member 0's look-ahead state names (group_sizes.h)
 };
 
 namespace gnn {
@@ -373,8 +385,14 @@ void launch_tile_step(gnn_mlp *h, int gsrc, int gdst, const NextBatch *next, con
 // ---- group_kernels.hip / group_kernels_gnn.hip: the grouped instances ----------------------------------
 const void *rb_group_function(const gnn_mlp *h); // the grouped row-block kernel of h's net, or null (h->rb must hold)
 // the launches of launch_small.hip for every member of h->grp: member 0's arguments, one grid row per member
+// (GroupLaunch::sized: the sized twins below)
 void launch_tile_step_group(gnn_mlp *h, int gsrc, int gdst, bool fwd, unsigned grid, const TileStepParams &t, int B);
-void launch_rowblock_group(gnn_mlp *h, unsigned grid, void *const *head_and_params); // (GNN_RB_HEAD_PARAMS + the RbParams)
+void launch_rowblock_group(gnn_mlp *h, int B, void *const *head_and_params); // (GNN_RB_HEAD_PARAMS + the RbParams)
+GroupArgs group_args(const GroupLaunch &g, int nbx, int B, const int *rows);
+// ---- group_kernels_sized.hip / group_kernels_sized_gnn.hip: the sized twins (every member with its own row count) --------
+const void *rb_group_sized_function(const gnn_mlp *h);
+void launch_tile_step_group_sized(gnn_mlp *h, int gsrc, int gdst, bool fwd, unsigned grid, const TileStepParams &t);
+void launch_rowblock_group_sized(gnn_mlp *h, void *const *head_and_params);
 
 // ---- sampler.hip ---------------------------------------------------------------------------------
 // validate(validation_size) (NNT:102-113) on the device: the summed loss of dataset rows [0, n) into *d_out (fp64, device)
@@ -443,13 +461,19 @@ int train_sampled_run(gnn_mlp *h, gnn_sampler_t *s, int iterations, int batch, d
 // region(lo, slice_bytes) when the device index region exists (member m's ring at lo + m * slice_bytes) and region(null, 0)
 // just before it is released; mixed_step(d_idx0, counts) steps ONE iteration whose batch sizes counts[m] differ between the
 // members -- member m's indices at d_idx0 + m * slice -- and leaves member 0's handle ready for the next grouped step.
+// sized() (gnn_mlp_group_train_sampled_sizes): the grouped launches take every member's own row count, so NO iteration is
+// mixed -- the loop calls step_sizes(rows, next_rows) in front of every step with the members' live rows in the iteration it is
+// about to step and in the one it announces (null: none announced), then steps member 0 as ever.
 struct SampledEach {
     virtual void region(const int32_t *lo, size_t slice_bytes) = 0;
     virtual int mixed_step(const int32_t *d_idx0, const int *counts) = 0;
+    virtual bool sized() const { return false; }
+    virtual void step_sizes(const int *rows, const int *next_rows) { (void)rows; (void)next_rows; }
     virtual ~SampledEach() {}
 };
-int train_sampled_run_each(gnn_mlp *h, gnn_sampler_t *const *samplers, int n, int iterations, int batch, double step, double momentum,
-                           int noise, SampledObserver *obs, SampledEach *each);
+// batches[m]: sampler m's nominal batch size (all equal unless each->sized()); every ring has the slot stride of the largest
+int train_sampled_run_each(gnn_mlp *h, gnn_sampler_t *const *samplers, int n, int iterations, const int *batches, double step,
+                           double momentum, int noise, SampledObserver *obs, SampledEach *each);
 gnn_sampler_t *sampler_copy(const gnn_sampler_t *s);
 void sampler_assign(gnn_sampler_t *dst, const gnn_sampler_t *src);
 

@@ -52,12 +52,15 @@ template <int OUTK> const void *mid4_runtime_instance(int L, int variant) {
     return with_layer_count(L, [&](auto NL) { return mid4_variant<RuntimeShape<decltype(NL)::value>, -1, OUTK>(variant); });
 }
 
-// ---- the row-block kernel: a family names the kernel template (single net / group) ------------------
+// ---- the row-block kernel: a family names the kernel template (single net / group / group with sizes) ----
 struct RbSingle {
     template <class SH, int ACT, int OUTK, bool BF> static const void *fn() { return GNN_KERNEL(rowblock_kernel<SH, ACT, OUTK, BF>); }
 };
 struct RbGroup {
     template <class SH, int ACT, int OUTK, bool BF> static const void *fn() { return GNN_KERNEL(rowblock_group_kernel<SH, ACT, OUTK, BF>); }
+};
+struct RbGroupSized { // (one batch size per member: group_kernels.h)
+    template <class SH, int ACT, int OUTK, bool BF> static const void *fn() { return GNN_KERNEL(rowblock_group_sized_kernel<SH, ACT, OUTK, BF>); }
 };
 
 // runtime extents; the bf16 form exists for nets of three and four layers.  Null otherwise, for both families: plan_rowblock

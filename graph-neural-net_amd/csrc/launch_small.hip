@@ -152,7 +152,7 @@ void fused_forward(gnn_mlp *h, const float *a0, const float *y, int B, bool back
         const float *hd_Wl = bf ? reinterpret_cast<const float *>(r.Wb[h->L - 2]) : r.W[h->L - 2];
         void *args[] = {&r.slabs, &hd_W1, &hd_Wl, &r.row_idx, &r.Y, &r.copy_idx, &r.B, &r.slab_rows, &r.ldy, &r};
         const unsigned grid = (unsigned)(pad_up(B) / 4);
-        if (h->grp) { launch_rowblock_group(h, grid, args); return; } // every member of a group (group_kernels.hip)
+        if (h->grp) { launch_rowblock_group(h, B, args); return; } // every member of a group (group_kernels.hip)
         launch_instance(h, GNN_K_MIDDLE, h->rb_fn, h->rb_jit, dim3(grid), dim3(RB_NT), h->rb_lds_bytes, args);
         return;
     }

@@ -175,7 +175,8 @@ void chain_gradient(gnn_mlp *h, const float *a0, const float *y, int B, bool fus
     // 784-300-100-10), and one step later the same copy is the gradient operand.  Without an announced sampled batch of the same
     // size it copies its own rows, for the gradient product only (the first step of a chain gathers that operand by index).
     const bool have_copy = la.xstage_valid && h->cur_idx != nullptr; // (made one step ago, or by the tile launch that made the slabs)
-    const bool rb_next = h->rb && fused_update && la.have_next && la.next.idx != nullptr && la.next.B == B;
+    // (a group call: the size test must hold for EVERY member -- GroupLaunch::next_same_rows, true unless the members have sizes of their own)
+    const bool rb_next = h->rb && fused_update && la.have_next && la.next.idx != nullptr && la.next.B == B && (!h->grp || h->grp->next_same_rows);
     const bool rb_cur = h->rb && !rb_next && !have_copy && h->cur_idx != nullptr;
     const bool staged = have_copy || rb_cur;
     la.step_takes_slabs();

@@ -149,13 +149,21 @@ void gnn::host::sampler_assign(gnn_sampler_t *dst, const gnn_sampler_t *src) { *
 
 // `obs` (handle.h: SampledObserver) is called behind every step and behind every sampler chunk, on the calling thread, with the
 // handle's stream holding everything enqueued so far: the observed loops below and the group's (group.hip) are this loop + one.
-// n samplers (n > 1: `each`, a group call with one sampler per member on member 0's handle): sampler m draws into ring m, and an
-// iteration whose n batch sizes differ is handed to each->mixed_step instead of being stepped here.
-static int train_sampled_impl(gnn_mlp_t *h, gnn_sampler_t *const *samplers, int n, int iterations, int batch, double step,
+// n samplers (n > 1: `each`, a group call with one sampler per member on member 0's handle): sampler m draws batches of
+// batches[m] into ring m, and an iteration whose n batch sizes differ is handed to each->mixed_step instead of being stepped
+// here -- unless each->sized(): the grouped launches then take every member's own size (each->step_sizes) and every iteration is
+// stepped here.  Unless sized, the n nominal sizes are equal.
+static int train_sampled_impl(gnn_mlp_t *h, gnn_sampler_t *const *samplers, int n, int iterations, const int *batches, double step,
                               double momentum, int noise, SampledObserver *obs, SampledEach *each) {
     TRY(check_handle(h));
     if (n < 1 || n > GROUP_MAX || (n > 1 && !each)) return fail(GNN_ERR_BAD_ARG, "bad sampler count");
-    for (int m = 0; m < n; m++) TRY(train_sampled_checks(h, samplers[m], iterations, batch, step, noise));
+    const bool sized = each && each->sized();
+    int batch = batches[0]; // the largest nominal size: the slot stride of every ring, so that member k's index pointer stays member 0's + k * idx_S
+    for (int m = 0; m < n; m++) {
+        if (!sized && batches[m] != batches[0]) return fail(GNN_ERR_BAD_ARG, "one batch size for all samplers");
+        TRY(train_sampled_checks(h, samplers[m], iterations, batches[m], step, noise));
+        batch = std::max(batch, batches[m]);
+    }
     if (iterations >= 64) try_specialize(h);
     // The exact epoch sampler is serial host work (~10 us per batch of 128: two Fenwick walks per
     // draw) of the same order as a step on the GPU, so it runs AHEAD on a worker thread, chunk by
@@ -202,7 +210,7 @@ static int train_sampled_impl(gnn_mlp_t *h, gnn_sampler_t *const *samplers, int 
         const int i0 = chunk_begin(c), i1 = chunk_end(c);
         int32_t *slot = idx + (size_t)m * slice_elems + (size_t)(c % kRing) * slot_elems;
         int *scnt = cnt.data() + (size_t)m * cnt_slice + (size_t)(c % kRing) * kc;
-        for (int i = i0; i < i1 && rc == GNN_OK; i++) rc = gnn_sampler_sample(samplers[m], batch, slot + (size_t)(i - i0) * batch, &scnt[i - i0]);
+        for (int i = i0; i < i1 && rc == GNN_OK; i++) rc = gnn_sampler_sample(samplers[m], batches[m], slot + (size_t)(i - i0) * batch, &scnt[i - i0]);
         if (rc != GNN_OK) *msg = gnn_mlp_last_error();
         return rc;
     });
@@ -248,7 +256,11 @@ static int train_sampled_impl(gnn_mlp_t *h, gnn_sampler_t *const *samplers, int 
         for (int m = 1; m < n; m++) if (dcnt[(size_t)m * cnt_slice + (size_t)slot * kc + at] != c0) return -1;
         return c0;
     };
-    int member_cnt[GROUP_MAX];
+    // every member's batch size of that iteration
+    auto member_counts = [&](int slot, int at, int *out) {
+        for (int m = 0; m < n; m++) out[m] = dcnt[(size_t)m * cnt_slice + (size_t)slot * kc + at];
+    };
+    int member_cnt[GROUP_MAX], next_cnt[GROUP_MAX];
     for (int c = 0; c < n_chunks && rc == GNN_OK; c++) {
         rc = release(false);
         if (rc != GNN_OK) break;
@@ -271,9 +283,20 @@ static int train_sampled_impl(gnn_mlp_t *h, gnn_sampler_t *const *samplers, int 
         const int slot = c % kRing, slot_n = (c + 1) % kRing;
         const size_t so = (size_t)slot * slot_elems, sn = (size_t)slot_n * slot_elems;
         for (int i = i0; i < i1 && rc == GNN_OK; i++) {
+            if (sized) { // every member with its own size, in the two grouped launches: the sizes travel beside the announcement
+                member_counts(slot, i - i0, member_cnt);
+                const int32_t *next_idx = nullptr;
+                if (h->chain && i + 1 < i1) { next_idx = d_idx + so + (size_t)(i + 1 - i0) * batch; member_counts(slot, i + 1 - i0, next_cnt); }
+                else if (h->chain && uploaded > c + 1) { next_idx = d_idx + sn; member_counts(slot_n, 0, next_cnt); }
+                each->step_sizes(member_cnt, next_idx ? next_cnt : nullptr);
+                if (next_idx) h->la.announce(NextBatch{h->DX, next_idx, next_cnt[0]});
+                rc = step_on_device_indices(h, d_idx + so + (size_t)(i - i0) * batch, member_cnt[0], step, momentum);
+                if (rc == GNN_OK && obs) rc = obs->after_step(i);
+                continue;
+            }
             const int B = common_count(slot, i - i0);
             if (B < 0) { // the members' batches differ in size (a refill shortened some): member after member, nothing announced
-                for (int m = 0; m < n; m++) member_cnt[m] = dcnt[(size_t)m * cnt_slice + (size_t)slot * kc + (i - i0)];
+                member_counts(slot, i - i0, member_cnt);
                 rc = each->mixed_step(d_idx + so + (size_t)(i - i0) * batch, member_cnt);
             } else {
                 if (h->chain && i + 1 < i1) { // the next draw of this chunk is already on the device
@@ -300,11 +323,11 @@ static int train_sampled_impl(gnn_mlp_t *h, gnn_sampler_t *const *samplers, int 
 
 int gnn::host::train_sampled_run(gnn_mlp *h, gnn_sampler_t *s, int iterations, int batch, double step, double momentum, int noise,
                                  SampledObserver *obs) {
-    return train_sampled_impl(h, &s, 1, iterations, batch, step, momentum, noise, obs, nullptr);
+    return train_sampled_impl(h, &s, 1, iterations, &batch, step, momentum, noise, obs, nullptr);
 }
-int gnn::host::train_sampled_run_each(gnn_mlp *h, gnn_sampler_t *const *samplers, int n, int iterations, int batch, double step,
+int gnn::host::train_sampled_run_each(gnn_mlp *h, gnn_sampler_t *const *samplers, int n, int iterations, const int *batches, double step,
                                       double momentum, int noise, SampledObserver *obs, SampledEach *each) {
-    return train_sampled_impl(h, samplers, n, iterations, batch, step, momentum, noise, obs, each);
+    return train_sampled_impl(h, samplers, n, iterations, batches, step, momentum, noise, obs, each);
 }
 
 namespace {
@@ -327,7 +350,7 @@ extern "C" {
 
 int gnn_mlp_train_sampled(gnn_mlp_t *h, gnn_sampler_t *s, int iterations, int batch, double step, double momentum,
                           int noise) { return guarded([&]() -> int {
-    return train_sampled_impl(h, &s, 1, iterations, batch, step, momentum, noise, nullptr, nullptr);
+    return train_sampled_impl(h, &s, 1, iterations, &batch, step, momentum, noise, nullptr, nullptr);
 }); }
 
 int gnn_mlp_train_sampled_observed(gnn_mlp_t *h, gnn_sampler_t *s, int iterations, int batch, double step, double momentum,
@@ -344,7 +367,7 @@ int gnn_mlp_train_sampled_observed(gnn_mlp_t *h, gnn_sampler_t *s, int iteration
     const bool rows_form = eval_block_rows(h, validation_size) >= validation_size && (int64_t)iterations * stride * 4 <= (1ll << 30);
     if (rows_form) TRY(drows.alloc(sizeof(float) * (size_t)iterations * (size_t)stride));
     LoneValidation obs(h, validation_size, dv.as<double>(), rows_form ? drows.as<float>() : nullptr, stride);
-    TRY(train_sampled_impl(h, &s, 1, iterations, batch, step, momentum, noise, &obs, nullptr));
+    TRY(train_sampled_impl(h, &s, 1, iterations, &batch, step, momentum, noise, &obs, nullptr));
     if (rows_form) {
         hipLaunchKernelGGL(sum_rows_kernel, dim3(iterations), dim3(256), 0, h->stream, RowSumParams{drows.as<float>(), stride, validation_size, dv.as<double>()});
         TRY_LAUNCHES(h);

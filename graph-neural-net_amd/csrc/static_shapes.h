@@ -2,7 +2,7 @@
 // kernel instances.  launch_small.hip instantiates the SoftmaxCrossEntropyNeuralNet forms (OUTK = 0), launch_small_gnn.hip
 // the GeneralNeuralNet forms (OUTK = 1: last_act + loss, GNN:215-218, GNN:267-271) -- two translation units so that the two
 // families compile side by side (each is ~70 s of hipcc); the grouped row-block instances likewise in group_kernels.hip and
-// group_kernels_gnn.hip.  The tables are function templates over the choices of instances.h: a unit compiles what it asks for.
+// group_kernels_gnn.hip, their sized twins in group_kernels_sized.hip and group_kernels_sized_gnn.hip.  The tables are function templates over the choices of instances.h: a unit compiles what it asks for.
 #pragma once
 #include "instances.h"
 
@@ -35,6 +35,7 @@ template <class Fam, int OUTK> const void *rb_static_table(int which, int act, b
 const void *mid4_static_general(int which, int act, int variant);
 const void *rb_static_general(int which, int act, bool bf);
 const void *rb_group_static_general(int which, int act, bool bf);
+const void *rb_group_sized_static_general(int which, int act, bool bf); // (group_kernels_sized_gnn.hip)
 
 } // namespace host
 } // namespace gnn

@@ -1,9 +1,10 @@
 // tile_step_bf16_body.inc -- the body of tile_step_bf16_kernel (tile_step_kernel.h), included INSIDE the kernels that run it:
 // the single-net kernel and its grouped twin (group_kernels.h).  In scope: the kernel argument `p` (TileStepParams),
-// the template parameters GSRC / GDST / FWD, and five macros that say who the kernel works for:
+// the template parameters GSRC / GDST / FWD, and nine macros that say who the kernel works for:
 // TS_BID (the workgroup's index in the tile map), TS_REL(ptr) (the net's copy of a pointer of `p`), TS_REL_LAYER(L) (the same
-// for a layer descriptor), TS_STEP_OVER_B and TS_MOMENTUM.  The single-net kernels define them as the plain expressions
-// they replace (tile_step_kernel.h), the grouped twins as member k's (group_kernels.h).  Text the kernels include, not a function
+// for a layer descriptor), TS_STEP_OVER_B and TS_MOMENTUM, and the four row counts TS_K / TS_K_TRUE (the current batch, padded /
+// live) and TS_NEXT_K / TS_NEXT_ROWS (the next one).  The single-net kernels define them as the plain expressions
+// they replace (tile_step_kernel.h), the grouped twins as member k's (group_kernels.h): block-uniform either way.  Text the kernels include, not a function
 // they call, so that the single-net kernels read `p` straight from their argument segment and compile to exactly the code
 // they had before the grouped twins existed.
     constexpr int LDA = TS_TM + 16;  // [k][m] bf16 image: 160-B rows (32*odd)
@@ -50,7 +51,7 @@
             if (k < kc && m0 + q * 8 < L.M) {
                 size_t a_row = (size_t)(k0 + k);
                 bool live = true;
-                if (li == 0 && TS_REL(p.row_idx)) { live = k0 + k < p.k_true; a_row = live ? (size_t)TS_REL(p.row_idx)[k0 + k] : 0; }
+                if (li == 0 && TS_REL(p.row_idx)) { live = k0 + k < TS_K_TRUE; a_row = live ? (size_t)TS_REL(p.row_idx)[k0 + k] : 0; }
                 if (live) va[i] = *reinterpret_cast<const bf16x8 *>(Ab + a_row * L.lda + m0 + q * 8);
             }
         }
@@ -60,7 +61,7 @@
             if (k < kc) vd = *reinterpret_cast<const bf16x8 *>(Db + (size_t)(k0 + k) * L.ldd + n0 + q * 8);
         }
     };
-    const int kc0 = (p.K < TS_KC) ? p.K : TS_KC;
+    const int kc0 = (TS_K < TS_KC) ? TS_K : TS_KC;
     if (GSRC == 1) load_grad(0, kc0);
     float4 w_old = make_float4(0.f, 0.f, 0.f, 0.f), v_old = w_old, g_in = w_old;
     if (e_ok) {
@@ -71,10 +72,10 @@
     // next batch: lane (fr, fg) of wave w -> row 16w + fr; per 32-wide k block the inputs 4fg..4fg+3 and 16+4fg..+3
     s16x4 vn[2][2];
     int next_row0 = wave * 16 + fr; // (as in tile_step_kernel: the index of a sampled next batch's row is fetched ahead)
-    if (fwd && TS_REL(p.next_idx) && next_row0 < p.next_rows) next_row0 = TS_REL(p.next_idx)[next_row0];
+    if (fwd && TS_REL(p.next_idx) && next_row0 < TS_NEXT_ROWS) next_row0 = TS_REL(p.next_idx)[next_row0];
     auto load_next = [&](int b0) {
         const int b = b0 + wave * 16 + fr;
-        const bool live = b < p.next_rows;
+        const bool live = b < TS_NEXT_ROWS;
         const size_t row = live ? (b0 == 0 ? (size_t)next_row0 : TS_REL(p.next_idx) ? (size_t)TS_REL(p.next_idx)[b] : (size_t)b) : 0;
         const __bf16 *src = TS_REL(p.Anb) + row * p.ldan + m0 + 4 * fg;
 #pragma unroll
@@ -91,8 +92,8 @@
     float4 g = g_in;
     if (GSRC == 1) {
         f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-        for (int k0 = 0; k0 < p.K; k0 += TS_KC) {
-            const int kc = (p.K - k0 < TS_KC) ? p.K - k0 : TS_KC;
+        for (int k0 = 0; k0 < TS_K; k0 += TS_KC) {
+            const int kc = (TS_K - k0 < TS_KC) ? TS_K - k0 : TS_KC;
             if (k0) { __syncthreads(); load_grad(k0, kc); }
 #pragma unroll
             for (int i = 0; i < 2; i++) {
@@ -140,9 +141,9 @@
     __syncthreads();
     float *slab = TS_REL(p.slabs) + (size_t)tm * p.slab_rows * p.ldz;
     const bf16x8 w0 = tr_frag(sW, TS_TN, 0, 0, lane), w1 = tr_frag(sW, TS_TN, 0, 32, lane); // A operand: rows n, k = m
-    for (int b0 = 0; b0 < p.next_K; b0 += TS_KC) {
+    for (int b0 = 0; b0 < TS_NEXT_K; b0 += TS_KC) {
         if (b0) load_next(b0);
-        if (TS_REL(p.stage_out_b) && tn < stage_cols && (((b0 + wave * 16) >> 4) % stage_cols) == tn && b0 + wave * 16 < p.next_K) { // (as in tile_step_kernel)
+        if (TS_REL(p.stage_out_b) && tn < stage_cols && (((b0 + wave * 16) >> 4) % stage_cols) == tn && b0 + wave * 16 < TS_NEXT_K) { // (as in tile_step_kernel)
             __bf16 *dst = TS_REL(p.stage_out_b) + (size_t)(b0 + wave * 16 + fr) * p.ldan + m0 + 4 * fg;
 #pragma unroll
             for (int kb = 0; kb < 2; kb++)
@@ -150,7 +151,7 @@
                 for (int hh = 0; hh < 2; hh++)
                     if (m0 + kb * 32 + hh * 16 + 4 * fg < L.M) *reinterpret_cast<s16x4 *>(dst + kb * 32 + hh * 16) = vn[kb][hh];
         }
-        if (b0 + wave * 16 < p.next_K) { // wave-uniform
+        if (b0 + wave * 16 < TS_NEXT_K) { // wave-uniform
             f32x4 z = {0.f, 0.f, 0.f, 0.f};
             z = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0, join8(vn[0][0], vn[0][1]), z, 0, 0, 0);
             z = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1, join8(vn[1][0], vn[1][1]), z, 0, 0, 0);

@@ -1,9 +1,10 @@
 // tile_step_body.inc -- the body of tile_step_kernel (tile_step_kernel.h), included INSIDE the kernels that run it:
 // the single-net kernel and its grouped twin (group_kernels.h).  In scope: the kernel argument `p` (TileStepParams),
-// the template parameters GSRC / GDST / FWD, and five macros that say who the kernel works for:
+// the template parameters GSRC / GDST / FWD, and nine macros that say who the kernel works for:
 // TS_BID (the workgroup's index in the tile map), TS_REL(ptr) (the net's copy of a pointer of `p`), TS_REL_LAYER(L) (the same
-// for a layer descriptor), TS_STEP_OVER_B and TS_MOMENTUM.  The single-net kernels define them as the plain expressions
-// they replace (tile_step_kernel.h), the grouped twins as member k's (group_kernels.h).  Text the kernels include, not a function
+// for a layer descriptor), TS_STEP_OVER_B and TS_MOMENTUM, and the four row counts TS_K / TS_K_TRUE (the current batch, padded /
+// live) and TS_NEXT_K / TS_NEXT_ROWS (the next one).  The single-net kernels define them as the plain expressions
+// they replace (tile_step_kernel.h), the grouped twins as member k's (group_kernels.h): block-uniform either way.  Text the kernels include, not a function
 // they call, so that the single-net kernels read `p` straight from their argument segment and compile to exactly the code
 // they had before the grouped twins existed.
     constexpr int NW = TS_THREADS / 64, NT = TS_THREADS, RPW = 1; // waves; threads; 16-row groups of a 128-row chunk per wave
@@ -44,10 +45,10 @@
     // ---- everything this block reads first, all loads in flight together ------------------------
     // gradient operands of the first K chunk
     float4 va[4 * RPW], vd[RPW];
-    const int kc0 = (p.K < TS_KC) ? p.K : TS_KC;
+    const int kc0 = (TS_K < TS_KC) ? TS_K : TS_KC;
     // A tile wholly inside its layer, a whole first chunk, rows in place: no bounds tests, no exec-mask branches -- every wave
     // runs this prologue before the first barrier, and a guarded 16-B load is ~13 instructions (see gemm_f32_kernel)
-    const bool interior = (m0 + TS_TM <= L.M) && (p.K >= TS_KC) && !(li == 0 && TS_REL(p.row_idx)) &&
+    const bool interior = (m0 + TS_TM <= L.M) && (TS_K >= TS_KC) && !(li == 0 && TS_REL(p.row_idx)) &&
                           (unsigned long long)TS_KC * (unsigned)(L.lda > L.ldd ? L.lda : L.ldd) < 0xffffffffull; // 32-bit offsets
     if (GSRC == 1 && interior) {
 #pragma unroll
@@ -68,7 +69,7 @@
             if (k < kc0 && m0 + q * 4 < L.M) {
                 size_t a_row = (size_t)k;
                 bool live = true;
-                if (li == 0 && TS_REL(p.row_idx)) { live = k < p.k_true; a_row = live ? (size_t)TS_REL(p.row_idx)[k] : 0; }
+                if (li == 0 && TS_REL(p.row_idx)) { live = k < TS_K_TRUE; a_row = live ? (size_t)TS_REL(p.row_idx)[k] : 0; }
                 if (live) va[i] = *reinterpret_cast<const float4 *>(L.A + a_row * L.lda + m0 + q * 4);
             }
         }
@@ -85,8 +86,8 @@
         if (GDST == 2) v_old = *reinterpret_cast<const float4 *>(L.V + e_off);
     }
     if (GSRC >= 2) g_in = ts_gradient_in<GSRC>(p, L, e_off, e_ok);
-    const bool next_plain = interior && fwd && !TS_REL(p.next_idx) && p.next_rows >= TS_KC && (unsigned long long)TS_KC * (unsigned)p.ldan < 0xffffffffull; // the first chunk of the next batch: all rows live, in place
-    const bool next_gather = (m0 + TS_TM <= L.M) && fwd && TS_REL(p.next_idx) && p.next_rows >= TS_KC;
+    const bool next_plain = interior && fwd && !TS_REL(p.next_idx) && TS_NEXT_ROWS >= TS_KC && (unsigned long long)TS_KC * (unsigned)p.ldan < 0xffffffffull; // the first chunk of the next batch: all rows live, in place
+    const bool next_gather = (m0 + TS_TM <= L.M) && fwd && TS_REL(p.next_idx) && TS_NEXT_ROWS >= TS_KC;
     const int stage_cols = (L.N / TS_TN) < 8 ? (L.N / TS_TN) : 8; // tile columns that share the staging copy's 16-row groups
     // the next batch's rows, already in MFMA fragment form: wave -> 16 batch rows of a 128-row chunk, lane
     // (fr, fq) -> row fr, inputs 16c + 4fq .. +3 of the tile (c = 0..3).  Straight to registers: A_0' is
@@ -98,7 +99,7 @@
 #pragma unroll
     for (int g = 0; g < RPW; g++) {
         next_row0[g] = (wave + g * NW) * 16 + fr;
-        if (fwd && TS_REL(p.next_idx) && next_row0[g] < p.next_rows) next_row0[g] = TS_REL(p.next_idx)[next_row0[g]];
+        if (fwd && TS_REL(p.next_idx) && next_row0[g] < TS_NEXT_ROWS) next_row0[g] = TS_REL(p.next_idx)[next_row0[g]];
     }
     auto load_next = [&](int b0) {
 #pragma unroll
@@ -117,7 +118,7 @@
                 for (int c = 0; c < 4; c++) vn[g][c] = *reinterpret_cast<const f32x4 *>(src + c * 16);
                 continue;
             }
-            const bool live = b < p.next_rows;
+            const bool live = b < TS_NEXT_ROWS;
             const size_t row = live ? (b0 == 0 ? (size_t)next_row0[g] : TS_REL(p.next_idx) ? (size_t)TS_REL(p.next_idx)[b] : (size_t)b) : 0;
             const float *src = TS_REL(p.An) + row * p.ldan + m0 + 4 * fq;
 #pragma unroll
@@ -138,8 +139,8 @@
     float4 g = g_in;
     if (GSRC == 1) {
         f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-        for (int k0 = 0; k0 < p.K; k0 += TS_KC) {
-            const int kc = (p.K - k0 < TS_KC) ? p.K - k0 : TS_KC; // a multiple of 16
+        for (int k0 = 0; k0 < TS_K; k0 += TS_KC) {
+            const int kc = (TS_K - k0 < TS_KC) ? TS_K - k0 : TS_KC; // a multiple of 16
             if (k0) {
                 __syncthreads();
 #pragma unroll
@@ -149,7 +150,7 @@
                     if (k < kc && m0 + q * 4 < L.M) {
                         size_t a_row = (size_t)(k0 + k);
                         bool live = true;
-                        if (li == 0 && TS_REL(p.row_idx)) { live = k0 + k < p.k_true; a_row = live ? (size_t)TS_REL(p.row_idx)[k0 + k] : 0; }
+                        if (li == 0 && TS_REL(p.row_idx)) { live = k0 + k < TS_K_TRUE; a_row = live ? (size_t)TS_REL(p.row_idx)[k0 + k] : 0; }
                         if (live) va[i] = *reinterpret_cast<const float4 *>(L.A + a_row * L.lda + m0 + q * 4);
                     }
                 }
@@ -252,20 +253,20 @@
     for (int c = 0; c < 4; c++)
 #pragma unroll
         for (int j = 0; j < 4; j++) wv[c][j] = wcol[(c * 16 + j) * LDW];
-    for (int b0 = 0; b0 < p.next_K; b0 += TS_KC) {
+    for (int b0 = 0; b0 < TS_NEXT_K; b0 += TS_KC) {
         if (b0) load_next(b0);
 #pragma unroll
         for (int g = 0; g < RPW; g++) {
             const int wr = (wave + g * NW) * 16; // this wave's row group of the chunk
             // the contiguous copy of a sampled next batch: every tile of this tile row holds the same rows; column tn copies
             // the 16-row groups g16 with g16 % n_tn == tn (all of them in one column made its 13 workgroups the kernel's last)
-            if (TS_REL(p.stage_out) && b0 + wr < p.next_K && (((b0 + wr) >> 4) % stage_cols) == tn % stage_cols && tn < stage_cols) { // (wave-uniform; rows past the batch and columns past M are zeros in vn)
+            if (TS_REL(p.stage_out) && b0 + wr < TS_NEXT_K && (((b0 + wr) >> 4) % stage_cols) == tn % stage_cols && tn < stage_cols) { // (wave-uniform; rows past the batch and columns past M are zeros in vn)
                 float *dst = TS_REL(p.stage_out) + (size_t)(b0 + wr + fr) * p.ldan + m0 + 4 * fq;
 #pragma unroll
                 for (int c = 0; c < 4; c++)
                     if (m0 + c * 16 + 4 * fq < L.M) *reinterpret_cast<f32x4 *>(dst + c * 16) = vn[g][c];
             }
-            if (b0 + wr < p.next_K) { // wave-uniform
+            if (b0 + wr < TS_NEXT_K) { // wave-uniform
                 f32x4 z0 = {0.f, 0.f, 0.f, 0.f}, z1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int c = 0; c < 4; c++) {

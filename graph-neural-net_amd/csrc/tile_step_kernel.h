@@ -207,6 +207,10 @@ template <int GSRC> __device__ __forceinline__ float4 ts_gradient_in(const TileS
 #define TS_REL_LAYER(L)
 #define TS_STEP_OVER_B p.step_over_b
 #define TS_MOMENTUM p.momentum
+#define TS_K p.K
+#define TS_K_TRUE p.k_true
+#define TS_NEXT_ROWS p.next_rows
+#define TS_NEXT_K p.next_K
 template <int GSRC, int GDST, bool FWD>
 __global__ __launch_bounds__(TS_THREADS) void tile_step_kernel(TileStepParams p) {
 #include "tile_step_body.inc"
@@ -230,5 +234,9 @@ __global__ __launch_bounds__(TS_THREADS) void tile_step_bf16_kernel(TileStepPara
 #undef TS_REL_LAYER
 #undef TS_STEP_OVER_B
 #undef TS_MOMENTUM
+#undef TS_K
+#undef TS_K_TRUE
+#undef TS_NEXT_ROWS
+#undef TS_NEXT_K
 
 } // namespace gnn

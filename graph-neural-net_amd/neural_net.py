@@ -497,11 +497,30 @@ class NetGroup:
             raise ValueError("samplers: one per member (%d), got %d" % (len(self), len(ss)))
         return (C.c_void_p * len(ss))(*[s._h for s in ss])
 
+    def _batches(self, batch, each):
+        """None for ONE batch size (an int); for a sequence of K ints, one per member, the int32 array -- which needs one sampler
+        per member too: one sampler's draws cannot serve two batch sizes."""
+        if np.ndim(batch) == 0:
+            return None
+        bs = [int(b) for b in batch]
+        if len(bs) != len(self):
+            raise ValueError("batch: one size per member (%d), got %d" % (len(self), len(bs)))
+        if each is None:
+            raise ValueError("a batch size per member needs a sampler per member: one sampler's draws cannot serve two batch sizes")
+        return (C.c_int32 * len(bs))(*bs)
+
     def train_sampled(self, sampler, iterations, batch, steps, momenta, noise=False):
         """NNT:82-90 for every member: with the draws of ONE sampler (trainer.Sampler), or, given a sequence of K samplers,
-        member k with the draws of sampler[k] -- K independent NeuralNetTrainer runs (gnn_mlp_group_train_sampled_each)."""
+        member k with the draws of sampler[k] -- K independent NeuralNetTrainer runs (gnn_mlp_group_train_sampled_each).
+        batch: an int, or with K samplers a sequence of K ints -- member k trains with batches of batch[k]
+        (gnn_mlp_group_train_sampled_sizes: the reference's sweep over step AND batch size, logs/trainLog.csv rows 1-3)."""
         st, mo = _per_member("steps", steps, len(self)), _per_member("momenta", momenta, len(self))
         each = self._samplers(sampler)
+        sizes = self._batches(batch, each)
+        if sizes is not None:
+            _capi.check(self._lib.gnn_mlp_group_train_sampled_sizes(self._h, each, int(iterations), sizes, _dp(st), _dp(mo),
+                                                                    int(bool(noise)), 0, None))
+            return
         if each is not None:
             _capi.check(self._lib.gnn_mlp_group_train_sampled_each(self._h, each, int(iterations), int(batch), _dp(st), _dp(mo),
                                                                    int(bool(noise)), 0, None))
@@ -513,14 +532,19 @@ class NetGroup:
         """NNT:68-72 / 75-79 for every member with the draws of ONE sampler, or of one sampler per member (a sequence of K):
         train_sampled, and after every iteration validate(validation_size) (NNT:102-113, the mean loss of the first rows of the
         data set; default rows // 100 + 1, NNT:65) of every member.  Returns the curves, an ndarray (iterations, K), from one
-        readback."""
+        readback.  batch: an int, or with K samplers a sequence of K ints (train_sampled)."""
         st, mo = _per_member("steps", steps, len(self)), _per_member("momenta", momenta, len(self))
         each = self._samplers(sampler)
+        sizes = self._batches(batch, each)
         if validation_size is None:
             if getattr(self, "_dataset_rows", None) is None:
                 raise ValueError("validation_size=None needs an uploaded data set")
             validation_size = self._dataset_rows // 100 + 1
         val = np.empty((max(int(iterations), 0), len(self)), dtype=np.float64)
+        if sizes is not None:
+            _capi.check(self._lib.gnn_mlp_group_train_sampled_sizes(self._h, each, int(iterations), sizes, _dp(st), _dp(mo),
+                                                                    int(bool(noise)), int(validation_size), _dp(val)))
+            return val
         if each is not None:
             _capi.check(self._lib.gnn_mlp_group_train_sampled_each(self._h, each, int(iterations), int(batch), _dp(st), _dp(mo),
                                                                    int(bool(noise)), int(validation_size), _dp(val)))
@@ -532,7 +556,8 @@ class NetGroup:
     @property
     def sampled_each_iterations(self):
         """(grouped, member_after_member) of the last call with one sampler per member: iterations stepped by the grouped
-        launches / member after member (batch sizes that differed at a refill, or a group without grouped launches)."""
+        launches / member after member (batch sizes that differed at a refill, or a group without grouped launches; with a
+        batch size per member every iteration of a group with grouped launches is grouped)."""
         a, b = C.c_int64(), C.c_int64()
         _capi.check(self._lib.gnn_mlp_group_sampled_each_iterations(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value

@@ -140,10 +140,15 @@ class NetGroupTrainer:
     def train(self, iterations, stepSizes, batchSize, momenta, noise=False, monitor=None, observers=None):
         """NNT:60-92 for every member (stepSizes / momenta: one value per member, or a scalar for all).  observers: K text
         streams, observers[k] receiving "%d,%.2f\n" % (i, validation loss of member k) per iteration (NNT:71); monitor: an
-        object with step() / finish(), stepped once per iteration."""
+        object with step() / finish(), stepped once per iteration.  batchSize: an int, or -- a trainer with a seed per member -- a
+        sequence of K ints, member k training with batches of batchSize[k] (NetGroup.train_sampled)."""
         if not iterations > 0:
             raise ValueError("iterations must be positive (NNT:62)")
-        if not (0 < batchSize < self.size):
+        if np.ndim(batchSize) != 0:
+            batchSize = [int(b) for b in batchSize]
+            if len(batchSize) != len(self.group):
+                raise ValueError("batchSize: one per member (%d), got %d" % (len(self.group), len(batchSize)))
+        if not all(0 < b < self.size for b in (batchSize if np.ndim(batchSize) != 0 else [batchSize])):
             raise ValueError("batchSize must be positive and below the data size (NNT:63)")
         if observers is not None and len(observers) != len(self.group):
             raise ValueError("observers: one stream per member (%d), got %d" % (len(self.group), len(observers)))

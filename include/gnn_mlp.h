@@ -297,7 +297,8 @@ int gnn_mlp_dp_replicas_identical(gnn_mlp_dp_t *h, int *identical);
 
 /* ---- a group of nets of one shape, trained side by side ------------------------------------------
  * The reference is run as SWEEPS: every run of MNISTTrainer is one net trained by NeuralNetTrainer with its own step size,
- * batch size or iteration count, each with Random(1) for its weights (SCE:111) and for its sampler (NNT:42).  A group holds
+ * batch size or iteration count, each with Random(1) for its weights (SCE:111) and for its sampler (NNT:42).  (Step sizes and
+ * momenta are per member in every training call; batch sizes in gnn_mlp_group_train_sampled_sizes.)  A group holds
  * K = n_members in [1, 16] nets of ONE shape / kind / activations / dtype on ONE device, and ONE copy of the training data;
  * on the two-launch path every launch of a group step serves all members (csrc/group_kernels.h).
  * Member k after any group call is bit for bit (weights, momentum, time) the lone handle created with seeds[k] that made the
@@ -354,7 +355,23 @@ int gnn_mlp_group_observed_launches(const gnn_mlp_group_t *g);
 int gnn_mlp_group_train_sampled_each(gnn_mlp_group_t *g, gnn_sampler_t *const *samplers, int iterations, int batch,
                                      const double *steps, const double *momenta, int noise,
                                      int validation_size, double *val_loss);
-/* of the LAST gnn_mlp_group_train_sampled_each call: iterations stepped by grouped launches / member after member */
+/* gnn_mlp_group_train_sampled_each with ONE BATCH SIZE PER MEMBER -- the reference's recorded sweep (logs/trainLog.csv rows 1-3:
+ * 784-100-50-10, 100 000 iterations, step 0.0042 / 0.0075 / 0.0100 with batch 2 / 4 / 8) as one call.  Member k ends bit for bit
+ * (weights, momentum, time) where the lone handle created with seeds[k] ends after gnn_mlp_train_sampled(samplers[k], iterations,
+ * batches[k], steps[k], momenta[k]); samplers[k] ends where it ends there.  val_loss null: unobserved; else val_loss[i * K + k] =
+ * validate(validation_size) of member k after iteration i, from one readback -- column k bit for bit the lone handle's
+ * gnn_mlp_train_sampled_observed curve (behind every grouped step each member is validated by the single-net forward pass).
+ * EVERY iteration is stepped by the two grouped launches, member k with its own live row count (csrc/group_kernels.h): a refill
+ * that shortens one member's batch (NNT:149-155) changes that member's rows and nothing else, so with equal batches this call
+ * also runs a seed-variance study without the member-after-member iterations of gnn_mlp_group_train_sampled_each.
+ * gnn_mlp_group_sampled_each_iterations then reports (iterations, 0); (0, iterations) for groups without grouped launches
+ * (as above), which run member k through gnn_mlp_train_sampled(_observed) with samplers[k], batches[k].
+ * Refused before any step and any draw: null batches, a batches[k] outside [1, max_batch] or not below the data set's rows
+ * (NNT:63) -> GNN_ERR_BAD_ARG; everything gnn_mlp_group_train_sampled_each refuses, with its codes. */
+int gnn_mlp_group_train_sampled_sizes(gnn_mlp_group_t *g, gnn_sampler_t *const *samplers, int iterations, const int32_t *batches,
+                                      const double *steps, const double *momenta, int noise,
+                                      int validation_size, double *val_loss);
+/* of the LAST gnn_mlp_group_train_sampled_each / _sizes call: iterations stepped by grouped launches / member after member */
 int gnn_mlp_group_sampled_each_iterations(const gnn_mlp_group_t *g, int64_t *grouped, int64_t *member_after_member);
 int gnn_mlp_group_synchronize(gnn_mlp_group_t *g);
 /* Evaluation of a whole group in one pass (csrc/group_eval_kernel.h).
