@@ -67,6 +67,12 @@ __device__ __forceinline__ const int32_t *group_rel(const int32_t *q, const Grou
 
 // the tile kernel bodies (tile_step_body.inc) for member blockIdx.y: its pointers, its step and momentum; the row counts are
 // member 0's (the plain fields) or, in the sized twins, its own
+// (TS_HEAD_PROLOGUE 0, TS_DEFER_WV 0: the struct-only, lookup-only prologue with W and V requested at the top -- the grouped
+// twins have no head arguments, tile_step_kernel.h, and compile to the code they had before the single-net kernels got theirs)
+#define TS_HEAD_PROLOGUE 0
+#define TS_DEFER_WV 0
+#define TS_HAS_ROW_IDX TS_REL(p.row_idx)
+#define TS_STAGE_N L.N
 #define TS_BID blockIdx.x
 #define TS_REL(q) group_rel((q), ga, ga_shift, ga_idx)
 #define TS_REL_LAYER(L) (L.A = TS_REL(L.A), L.D = TS_REL(L.D), L.W = TS_REL(L.W), L.V = TS_REL(L.V), L.G = TS_REL(L.G))
@@ -120,6 +126,10 @@ __global__ __launch_bounds__(TS_THREADS) void tile_step_bf16_group_sized_kernel(
     GNN_GROUP_ROW_COUNTS
 #include "tile_step_bf16_body.inc"
 }
+#undef TS_HEAD_PROLOGUE
+#undef TS_DEFER_WV
+#undef TS_HAS_ROW_IDX
+#undef TS_STAGE_N
 #undef TS_BID
 #undef TS_REL
 #undef TS_REL_LAYER

@@ -116,6 +116,7 @@ struct gnn_mlp {
     int ts_tiles = 0, ts_tiles0 = 0; // blocks of all layers / of layer 0 alone
     uint32_t *ts_map = nullptr, *ts_map0 = nullptr; // workgroup -> tile of the two grids (make_tile_map), device memory
     bool ts_map_args = false; uint32_t ts_map_words[2][gnn::TS_MAP_ARGS / 2]; // ... and packed for the kernel arguments ([0]: all layers, [1]: layer 0)
+    gnn::TileHead ts_head[2] = {{0, 0}, {0, 0}}; // the two words that name the regular slots' tiles without a lookup (make_tile_head; {0, 0}: the plan is not regular), same order
     float *slabs = nullptr;
     int n_slabs = 0;
     std::string plan_note;    // why the net is NOT on the two-launch path (empty when it is): gnn_mlp_plan_note
@@ -185,6 +186,7 @@ struct gnn_mlp {
     bool env_chain_off = false;  // GNN_MLP_CHAIN=0: three launches per step (fwd_first / middle4 / grad_update)
     int first_wavek_rows = 256;  // launch_fwd_first: blocks of at least this many rows take the (ragged) wave-K GEMM (GNN_MLP_FIRST_WAVEK_ROWS; 0 = never)
     int first_gemm_rows = 2048;  // launch_fwd_first: blocks of at least this many rows take gemm_f32_kernel (GNN_MLP_FIRST_GEMM_ROWS; 0 = never)
+    bool env_tile_head_off = false; // GNN_MLP_TILE_HEAD=0: the tile kernel's earlier prologue -- every argument from the struct, every tile from the lookup, W and V requested at the top
     bool env_rb_off = false;     // GNN_MLP_ROWBLOCK=0: middle4_kernel<.., SLABS> as the two-launch step's row-block kernel (round 2's form)
 };
 

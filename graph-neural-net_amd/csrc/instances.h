@@ -76,7 +76,8 @@ template <class Fam, int OUTK> const void *rb_runtime_instance(int L, bool bf) {
 
 // ---- the tile-owner kernel: (gsrc, gdst, fwd) as in tile_step_kernel.h -------------------------------------
 // A family names the kernel template and says whether it has the peer forms (GSRC 3 / 4: dp.hip); a family without them
-// gets null for those (the grouped kernels static_assert GSRC <= 2, so they are not even named).  gdst is read only with
+// gets null for those (the grouped kernels static_assert GSRC <= 2, so they are not even named).  The single-net families are
+// templates on HEAD (launch_small.hip): the head-argument prologue of tile_step_kernel.h, or, GNN_MLP_TILE_HEAD=0, the earlier one.  gdst is read only with
 // gsrc == 1, fwd not with gsrc == 0 or <1, 1>: the callers pass (0, 0, .), (1, 1, .), (1, 2, .), (2..4, 2, .) only.
 template <class Fam> const void *tile_step_instance(int gsrc, int gdst, bool fwd) {
     auto fwd_or_not = [&](auto S) {

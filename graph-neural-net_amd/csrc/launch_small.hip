@@ -168,13 +168,14 @@ void fused_forward(gnn_mlp *h, const float *a0, const float *y, int B, bool back
 
 // ---- tile_step_kernel launches ------------------------------------------------------------------
 // the single-net families of tile_step_instance (instances.h), peer forms included
-struct TileF32 {
+// (HEAD = false, GNN_MLP_TILE_HEAD=0: the kernels with their earlier prologue -- arguments from the struct, every tile by lookup, W and V at the top)
+template <bool HEAD> struct TileF32 {
     static constexpr bool kPeerForms = true;
-    template <int S, int D, bool F> static const void *fn() { return GNN_KERNEL(tile_step_kernel<S, D, F>); }
+    template <int S, int D, bool F> static const void *fn() { return GNN_KERNEL(tile_step_kernel<S, D, F, HEAD, HEAD>); }
 };
-struct TileBf16 {
+template <bool HEAD> struct TileBf16 {
     static constexpr bool kPeerForms = true;
-    template <int S, int D, bool F> static const void *fn() { return GNN_KERNEL(tile_step_bf16_kernel<S, D, F>); }
+    template <int S, int D, bool F> static const void *fn() { return GNN_KERNEL(tile_step_bf16_kernel<S, D, F, HEAD>); }
 };
 
 // gsrc / gdst / fwd as in tile_step_kernel.h; fwd_only_layer0: the grid covers layer 0's tiles only
@@ -209,8 +210,15 @@ void launch_tile_step(gnn_mlp *h, int gsrc, int gdst, const NextBatch *next, con
         if (fwd) t.Anb = next_staged ? h->xstage_b[stage_dst] : a0_bf16(h, next->a0);
     }
     if (h->grp) { launch_tile_step_group(h, gsrc, gdst, fwd, grid.x, t, B); return; } // every member of a group (group_kernels.hip)
-    const void *fn = h->dtype == GNN_DTYPE_BF16 ? tile_step_instance<TileBf16>(gsrc, gdst, fwd) : tile_step_instance<TileF32>(gsrc, gdst, fwd);
-    void *args[] = {&t};
+    const bool bf = h->dtype == GNN_DTYPE_BF16, head = !h->env_tile_head_off;
+    const void *fn = bf ? (head ? tile_step_instance<TileBf16<true>>(gsrc, gdst, fwd) : tile_step_instance<TileBf16<false>>(gsrc, gdst, fwd))
+                        : (head ? tile_step_instance<TileF32<true>>(gsrc, gdst, fwd) : tile_step_instance<TileF32<false>>(gsrc, gdst, fwd));
+    // (the head arguments: tile_step_kernel.h, GNN_TS_HEAD_PARAMS -- in this order; the bf16 kernel takes layer 0's bf16 A and D in the first two slots)
+    const GradLayer &l0 = t.layer[0];
+    const float *hd_A = bf ? reinterpret_cast<const float *>(t.Ab[0]) : l0.A, *hd_D = bf ? reinterpret_cast<const float *>(t.Db[0]) : l0.D;
+    int hd_Kr = t.K | (t.row_idx ? 1 : 0); // (the padded rows are a multiple of 16)
+    TileHead hd = h->ts_head[fwd_only ? 1 : 0];
+    void *args[] = {&hd_A, &hd_D, &t.layer[0].W, &t.layer[0].V, &t.layer[0].lda, &t.layer[0].ldd, &t.layer[0].M, &hd_Kr, &hd.geo, &hd.kx, &t};
     launch_instance(h, cls, fn, nullptr, grid, block, 0, args);
 }
 

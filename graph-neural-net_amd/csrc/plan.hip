@@ -138,6 +138,9 @@ void plan_chain(gnn_mlp *h) {
         h->ts_tiles = (int)all.size();
         h->ts_tiles0 = (int)first.size();
         h->ts_map_args = pack_tile_map(all, h->ts_map_words[0]) && pack_tile_map(first, h->ts_map_words[1]);
+        // the regular slots' decode words, each checked slot by slot against its map ({0, 0} = every slot by lookup)
+        h->ts_head[0] = make_tile_head(ml, all);
+        h->ts_head[1] = make_tile_head(ml, first);
     }
     t.slabs = h->slabs; t.slab_rows = h->cap_rows; t.ldz = h->ld[1];
     h->chain = true;

@@ -1,6 +1,6 @@
 // tile_step_bf16_body.inc -- the body of tile_step_bf16_kernel (tile_step_kernel.h), included INSIDE the kernels that run it:
 // the single-net kernel and its grouped twin (group_kernels.h).  In scope: the kernel argument `p` (TileStepParams),
-// the template parameters GSRC / GDST / FWD, and nine macros that say who the kernel works for:
+// the template parameters GSRC / GDST / FWD, TS_HEAD_PROLOGUE / TS_HEAD (tile_step_kernel.h), and nine macros that say who the kernel works for:
 // TS_BID (the workgroup's index in the tile map), TS_REL(ptr) (the net's copy of a pointer of `p`), TS_REL_LAYER(L) (the same
 // for a layer descriptor), TS_STEP_OVER_B and TS_MOMENTUM, and the four row counts TS_K / TS_K_TRUE (the current batch, padded /
 // live) and TS_NEXT_K / TS_NEXT_ROWS (the next one).  The single-net kernels define them as the plain expressions
@@ -20,6 +20,15 @@
     // ten workgroups) is requested at once, beside the map entry that names the tile, not behind it
     int li, tm, tn;
     GradLayer L = p.layer[0];
+#if TS_HEAD_PROLOGUE
+    // (as in tile_step_body.inc: a regular slot takes its tile from the workgroup's id and its first loads' addresses from the
+    //  preloaded head arguments; the first two pointer slots carry the bf16 A and D of layer 0)
+    const bool regular = TS_HEAD && ts_head_tile(hd_geo, hd_kx, (int)TS_BID, tm, tn); // (block-uniform)
+    if (regular) {
+        li = 0;
+        L.W = hd_W; L.V = hd_V; L.lda = hd_lda; L.ldd = hd_ldd; L.M = hd_M;
+    } else
+#endif
     if (p.map_in_args) {
         const uint32_t w = p.map_words[TS_BID >> 1], e = (TS_BID & 1) ? w >> 16 : w & 0xffffu;
         if (e == 0xffffu) return;
@@ -33,8 +42,12 @@
     TS_REL_LAYER(L);
     const int m0 = tm * TS_TM, n0 = tn * TS_TN;
     const bool fwd = FWD && li == 0;
+#if TS_HEAD_PROLOGUE
+    const __bf16 *Ab = regular ? reinterpret_cast<const __bf16 *>(hd_A) : p.Ab[li], *Db = regular ? reinterpret_cast<const __bf16 *>(hd_D) : p.Db[li];
+#else
     const __bf16 *Ab = TS_REL(p.Ab[li]), *Db = TS_REL(p.Db[li]);
-    const int stage_cols = (L.N / TS_TN) < 8 ? (L.N / TS_TN) : 8; // tile columns that share the staging copy's 16-row groups
+#endif
+    const int stage_cols = (TS_STAGE_N / TS_TN) < 8 ? (TS_STAGE_N / TS_TN) : 8; // tile columns that share the staging copy's 16-row groups (read with fwd only: layer 0)
 
     const int er = (t >> 6) * 16 + fr, eq = fg; // (as in tile_step_kernel: the accumulator layout of the transposed product)
     const bool e_ok = t < 256 && (m0 + er < L.M);
@@ -51,7 +64,7 @@
             if (k < kc && m0 + q * 8 < L.M) {
                 size_t a_row = (size_t)(k0 + k);
                 bool live = true;
-                if (li == 0 && TS_REL(p.row_idx)) { live = k0 + k < TS_K_TRUE; a_row = live ? (size_t)TS_REL(p.row_idx)[k0 + k] : 0; }
+                if (li == 0 && TS_HAS_ROW_IDX) { live = k0 + k < TS_K_TRUE; a_row = live ? (size_t)TS_REL(p.row_idx)[k0 + k] : 0; }
                 if (live) va[i] = *reinterpret_cast<const bf16x8 *>(Ab + a_row * L.lda + m0 + q * 8);
             }
         }

@@ -1,6 +1,6 @@
 // tile_step_body.inc -- the body of tile_step_kernel (tile_step_kernel.h), included INSIDE the kernels that run it:
 // the single-net kernel and its grouped twin (group_kernels.h).  In scope: the kernel argument `p` (TileStepParams),
-// the template parameters GSRC / GDST / FWD, and nine macros that say who the kernel works for:
+// the template parameters GSRC / GDST / FWD, TS_HEAD_PROLOGUE / TS_HEAD / TS_DEFER_WV / TS_HAS_ROW_IDX (tile_step_kernel.h), and nine macros that say who the kernel works for:
 // TS_BID (the workgroup's index in the tile map), TS_REL(ptr) (the net's copy of a pointer of `p`), TS_REL_LAYER(L) (the same
 // for a layer descriptor), TS_STEP_OVER_B and TS_MOMENTUM, and the four row counts TS_K / TS_K_TRUE (the current batch, padded /
 // live) and TS_NEXT_K / TS_NEXT_ROWS (the next one).  The single-net kernels define them as the plain expressions
@@ -17,11 +17,22 @@
     const int t = threadIdx.x, lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int fr = lane & 15, fq = lane >> 4;
+    TS_STAMP(0);
 
     // by value: one batch of scalar loads, not one round trip per field as it is first used; layer 0's descriptor (nine of
     // ten workgroups) is requested at once, beside the map entry that names the tile, not behind it
     int li, tm, tn;
     GradLayer L = p.layer[0];
+#if TS_HEAD_PROLOGUE
+    // a regular slot (tile_step_kernel.h, ts_head_tile: the full layer-0 tiles) takes its tile from the workgroup's id and
+    // everything its first vector loads and the `interior` test need from the preloaded head arguments: no scalar load
+    // stands in front of them.  Of the struct's descriptor only G is read then (the forms that store or fetch a gradient).
+    const bool regular = TS_HEAD && ts_head_tile(hd_geo, hd_kx, (int)TS_BID, tm, tn); // (block-uniform)
+    if (regular) {
+        li = 0;
+        L.A = hd_A; L.D = hd_D; L.W = hd_W; L.V = hd_V; L.lda = hd_lda; L.ldd = hd_ldd; L.M = hd_M;
+    } else
+#endif
     if (p.map_in_args) {
         const uint32_t w = p.map_words[TS_BID >> 1], e = (TS_BID & 1) ? w >> 16 : w & 0xffffu;
         if (e == 0xffffu) return;
@@ -48,7 +59,7 @@
     const int kc0 = (TS_K < TS_KC) ? TS_K : TS_KC;
     // A tile wholly inside its layer, a whole first chunk, rows in place: no bounds tests, no exec-mask branches -- every wave
     // runs this prologue before the first barrier, and a guarded 16-B load is ~13 instructions (see gemm_f32_kernel)
-    const bool interior = (m0 + TS_TM <= L.M) && (TS_K >= TS_KC) && !(li == 0 && TS_REL(p.row_idx)) &&
+    const bool interior = (m0 + TS_TM <= L.M) && (TS_K >= TS_KC) && !(li == 0 && TS_HAS_ROW_IDX) &&
                           (unsigned long long)TS_KC * (unsigned)(L.lda > L.ldd ? L.lda : L.ldd) < 0xffffffffull; // 32-bit offsets
     if (GSRC == 1 && interior) {
 #pragma unroll
@@ -80,15 +91,20 @@
             if (k < kc0) vd[i] = *reinterpret_cast<const float4 *>(L.D + (size_t)k * L.ldd + n0 + q * 4);
         }
     }
+    TS_STAMP(1);
+    // the tile's W and V.  With a gradient product to wait for (GSRC == 1, TS_DEFER_WV) they are requested BEHIND the first
+    // barrier: they are first needed at the update, after the gradient MFMAs, and in front of the barrier their 8 KB share
+    // the CU's load path with the 40 KB of gradient operands the barrier waits for.
+    constexpr bool defer_wv = TS_DEFER_WV && GSRC == 1;
     float4 w_old = make_float4(0.f, 0.f, 0.f, 0.f), v_old = w_old, g_in = w_old;
-    if (e_ok) {
+    if (!defer_wv && e_ok) {
         if (GDST == 2 || FWD) w_old = *reinterpret_cast<const float4 *>(L.W + e_off);
         if (GDST == 2) v_old = *reinterpret_cast<const float4 *>(L.V + e_off);
     }
     if (GSRC >= 2) g_in = ts_gradient_in<GSRC>(p, L, e_off, e_ok);
     const bool next_plain = interior && fwd && !TS_REL(p.next_idx) && TS_NEXT_ROWS >= TS_KC && (unsigned long long)TS_KC * (unsigned)p.ldan < 0xffffffffull; // the first chunk of the next batch: all rows live, in place
     const bool next_gather = (m0 + TS_TM <= L.M) && fwd && TS_REL(p.next_idx) && TS_NEXT_ROWS >= TS_KC;
-    const int stage_cols = (L.N / TS_TN) < 8 ? (L.N / TS_TN) : 8; // tile columns that share the staging copy's 16-row groups
+    const int stage_cols = (TS_STAGE_N / TS_TN) < 8 ? (TS_STAGE_N / TS_TN) : 8; // tile columns that share the staging copy's 16-row groups (read with fwd only: layer 0)
     // the next batch's rows, already in MFMA fragment form: wave -> 16 batch rows of a 128-row chunk, lane
     // (fr, fq) -> row fr, inputs 16c + 4fq .. +3 of the tile (c = 0..3).  Straight to registers: A_0' is
     // k-contiguous, no wave shares another's rows, and the product below needs no LDS image of it.
@@ -173,6 +189,11 @@
             }
             __syncthreads();
             if (k0 == 0) {
+                TS_STAMP(2);
+                if (defer_wv && e_ok) { // (the batch has at least one row, so this trip runs) needed at the update: in front of the rows below, which are needed later still
+                    if (GDST == 2 || FWD) w_old = *reinterpret_cast<const float4 *>(L.W + e_off);
+                    if (GDST == 2) v_old = *reinterpret_cast<const float4 *>(L.V + e_off);
+                }
                 if (fwd) load_next(0); // lands under the gradient MFMAs and the update
             }
             if (wave < 4) {
@@ -238,6 +259,7 @@
             ts_store16(L.V + e_off, (f32x4){adj.x, adj.y, adj.z, adj.w});
         }
     }
+    TS_STAMP(3);
     if (!fwd) return;
 
     // ---- the next batch's first-layer sums over this tile's 64 input neurons ---------------------
@@ -281,3 +303,4 @@
             }
         }
     }
+    TS_STAMP(3);

@@ -160,6 +160,63 @@ inline bool pack_tile_map(const std::vector<uint32_t> &map, uint32_t (&words)[TS
     return true;
 }
 
+// ---- the regular slots: workgroup -> tile WITHOUT a lookup ------------------------------------------------------------
+// make_tile_map puts the full layer-0 tiles of XCD x in the order of x's rectangle (row-major inside it), behind the
+// slots at the front that share a CU (an XCD with fewer light tiles than such slots gives them the FIRST tiles of its
+// rectangle -- the order goes on from there; k_x is the slot of the rectangle's first tile).  For those slots the tile is arithmetic in the workgroup's id and two dwords that
+// travel as leading kernel arguments (GNN_TS_HEAD_PARAMS below: preloaded into SGPRs), so a full layer-0 workgroup -- the
+// heavy ones, 228 of 284 on 784-300-100-10 -- forms the addresses of its first vector loads with no scalar load at all:
+//   geo = rm | rn << 6 | xs << 14 | full_m << 16 | tiles_n << 23   (the rectangles of make_xcd_tiling(full_m, tiles_n))
+//   kx  = k_x, four bits per XCD
+// Every other slot (the pair slots, the small layers, a partial last tile row, idle entries) keeps the lookup.  The MAP
+// stays the truth: make_tile_head evaluates the decode for every slot and hands out {0, 0} -- no regular slot -- unless
+// each slot the decode claims names exactly its map entry.
+struct TileHead { uint32_t geo, kx; };
+// id -> (tm, tn) of a regular slot; false: not regular, use the lookup.  No integer division: j / w through the
+// reciprocal.  (j + 0.5) / w is at least 0.5 / w >= 2^-9 away from an integer and below rm <= 63, so a relative error of
+// a few 2^-24 (the device's v_rcp_f32 is good to 1 ulp, the host divides) moves it by less than 2^-16: the same
+// integer on both sides.
+__host__ __device__ __forceinline__ bool ts_head_tile(uint32_t geo, uint32_t kx, int id, int &tm, int &tn) {
+    const int rm = (int)(geo & 63u), rn = (int)((geo >> 6) & 255u), xs = (int)((geo >> 14) & 3u);
+    const int full_m = (int)((geo >> 16) & 127u), tiles_n = (int)(geo >> 23);
+    const int x = id & 7, j = (id >> 3) - (int)((kx >> (4 * x)) & 15u);
+    const int r0 = (x >> xs) * rm, c0 = (x & ((1 << xs) - 1)) * rn;
+    const int h = full_m - r0 < rm ? full_m - r0 : rm, w = tiles_n - c0 < rn ? tiles_n - c0 : rn; // (clipped at the matrix edge)
+    if (j < 0 || h <= 0 || w <= 0 || j >= h * w) return false;
+#if defined(__HIP_DEVICE_COMPILE__)
+    const int q = (int)(((float)j + 0.5f) * __builtin_amdgcn_rcpf((float)w));
+#else
+    const int q = (int)(((float)j + 0.5f) * (1.0f / (float)w));
+#endif
+    tm = r0 + q; tn = c0 + (j - q * w);
+    return true;
+}
+// the two words of a map made by make_tile_map(layers, ...); {0, 0} when a field does not fit, a k_x is
+// above 15, or one slot the decode calls regular is not the map's entry (force_mismatch: tests only)
+inline TileHead make_tile_head(const TileMapLayer *layers, const std::vector<uint32_t> &map, bool force_mismatch = false) {
+    const int tiles_m = (layers[0].M + TS_TM - 1) / TS_TM, tiles_n = layers[0].N / TS_TN;
+    int full_m = 0;
+    for (int tm = 0; tm < tiles_m; tm++) if (layers[0].M - tm * TS_TM > TS_TM / 2) full_m = tm + 1;
+    if (full_m == 0 || map.empty() || map.size() % 8 != 0) return TileHead{0, 0};
+    const XcdTiling rect = make_xcd_tiling(full_m, tiles_n);
+    if (rect.rm > 63 || rect.rn > 255 || rect.xs > 3 || full_m > 127 || tiles_n > 511) return TileHead{0, 0};
+    TileHead hd{(uint32_t)rect.rm | (uint32_t)rect.rn << 6 | (uint32_t)rect.xs << 14 | (uint32_t)full_m << 16 | (uint32_t)tiles_n << 23, 0};
+    for (int x = 0; x < 8; x++) { // k_x: the slot of the rectangle's first tile
+        const int r0 = (x >> rect.xs) * rect.rm, c0 = (x & (rect.xn - 1)) * rect.rn;
+        if (r0 >= full_m || c0 >= tiles_n) continue; // (a rectangle past the matrix edge: no tile, no regular slot)
+        size_t k = 0;
+        while (k * 8 < map.size() && map[k * 8 + x] != ((uint32_t)r0 << 4 | (uint32_t)c0 << 18)) k++;
+        if (k > 15) return TileHead{0, 0};
+        hd.kx |= (uint32_t)k << (4 * x);
+    }
+    if (force_mismatch) hd.kx ^= 1u;
+    for (size_t id = 0; id < map.size(); id++) {
+        int tm = 0, tn = 0;
+        if (ts_head_tile(hd.geo, hd.kx, (int)id, tm, tn) && map[id] != ((uint32_t)tm << 4 | (uint32_t)tn << 18)) return TileHead{0, 0};
+    }
+    return hd;
+}
+
 // 16-B store that is written THROUGH the XCD's L2 (sc1): the line does not stay dirty, so the end of the kernel has nothing
 // to write back for it (a kernel boundary costs ~B / 6 TB/s for B dirty bytes, MI355X_MICROARCH.md, row `boundary`), and the
 // bytes leave while the kernel still runs.  Inline asm (the compiler has no spelling for it on a 16-B vector); the s_nop
@@ -202,17 +259,35 @@ template <int GSRC> __device__ __forceinline__ float4 ts_gradient_in(const TileS
 
 // The slabs and the updated masters are stored write-through (ts_store16).
 
+// The arguments a layer-0 workgroup's FIRST instructions need travel ahead of the struct (the library is built
+// with -mllvm -amdgpu-kernarg-preload-count=16, as for GNN_RB_HEAD_PARAMS in rowblock_kernel.h): layer 0's A, D, W, V (the
+// bf16 kernel: its bf16 A and D in the first two slots), lda, ldd, M, hd_Kr = the padded batch rows (a multiple of 16) | 1
+// when a row index is in use, and the two words of ts_head_tile.  FOURTEEN dwords, and no more: of the 16 user SGPRs the
+// kernel-argument pointer takes two, and a fifteenth argument came back as a scalar load in front of the decode.  As fields of the by-value struct they came through the scalar cache from a
+// kernel-argument line nothing had touched, in front of the first vector load.  Everything else -- what the forward half
+// needs behind the barrier included -- stays in the struct; so does the descriptor of every slot that is not regular.
+// HEAD = false (GNN_MLP_TILE_HEAD=0): the prologue as it was, every argument from the struct and every tile from the
+// lookup -- the reference point of the bitwise test.  DEFER_WV: tile_step_body.inc.  A launch passes the head, then p.
+#define GNN_TS_HEAD_PARAMS const float *hd_A, const float *hd_D, float *hd_W, float *hd_V, int hd_lda, int hd_ldd, int hd_M, int hd_Kr, uint32_t hd_geo, uint32_t hd_kx
+#define TS_HEAD_PROLOGUE 1
+#define TS_HEAD HEAD
+#define TS_DEFER_WV DEFER_WV
+#ifndef TS_STAMP
+#define TS_STAMP(slot) // (tools/tile_probe.hip defines it in its stamped build; nothing is stamped in the library)
+#endif
 #define TS_BID blockIdx.x
 #define TS_REL(q) (q)
 #define TS_REL_LAYER(L)
 #define TS_STEP_OVER_B p.step_over_b
 #define TS_MOMENTUM p.momentum
-#define TS_K p.K
+#define TS_K (HEAD ? (hd_Kr & ~1) : p.K)
 #define TS_K_TRUE p.k_true
+#define TS_HAS_ROW_IDX (HEAD ? (hd_Kr & 1) != 0 : p.row_idx != nullptr)
+#define TS_STAGE_N p.layer[0].N // (layer 0's N where it is used, behind the barrier: as a field of L its scalar load was waited for at the top)
 #define TS_NEXT_ROWS p.next_rows
 #define TS_NEXT_K p.next_K
-template <int GSRC, int GDST, bool FWD>
-__global__ __launch_bounds__(TS_THREADS) void tile_step_kernel(TileStepParams p) {
+template <int GSRC, int GDST, bool FWD, bool HEAD = true, bool DEFER_WV = true>
+__global__ __launch_bounds__(TS_THREADS) void tile_step_kernel(GNN_TS_HEAD_PARAMS, TileStepParams p) {
 #include "tile_step_body.inc"
 }
 
@@ -225,10 +300,15 @@ __global__ __launch_bounds__(TS_THREADS) void tile_step_kernel(TileStepParams p)
 // they are and read with ds_read_b64_tr_b16; the weight tile [m][n] is k-major for the forward product too.
 // ------------------------------------------------------------------------------------------------
 
-template <int GSRC, int GDST, bool FWD>
-__global__ __launch_bounds__(TS_THREADS) void tile_step_bf16_kernel(TileStepParams p) {
+template <int GSRC, int GDST, bool FWD, bool HEAD = true>
+__global__ __launch_bounds__(TS_THREADS) void tile_step_bf16_kernel(GNN_TS_HEAD_PARAMS, TileStepParams p) {
 #include "tile_step_bf16_body.inc"
 }
+#undef TS_HEAD_PROLOGUE
+#undef TS_HEAD
+#undef TS_DEFER_WV
+#undef TS_HAS_ROW_IDX
+#undef TS_STAGE_N
 #undef TS_BID
 #undef TS_REL
 #undef TS_REL_LAYER

@@ -1,10 +1,22 @@
 // tile_probe.hip -- development harness (not shipped): tile_step_kernel on the 784-300-100-10 / B = 128
-// shapes with random data: HIP-event time per call of every mode, workgroup -> tile maps and sampled next batches.
+// shapes with random data: HIP-event time per call of every mode, workgroup -> tile maps and sampled next batches, and the
+// prologue variants (head arguments / W and V behind the first barrier) against the form they replace, in one process.
+// Build as the library is built (-mllvm -amdgpu-kernarg-preload-count=16).  -DTILE_PROBE_STAMPS: the stamped build -- thread 0
+// of every workgroup records the cycle counter at the kernel's top, behind its first vector loads, behind the first barrier and
+// at its end; the times of THAT build are not the kernel's (use the plain build's lines), its stamps say where a workgroup's time goes.
+#ifdef TILE_PROBE_STAMPS
+#include <hip/hip_runtime.h>
+__device__ unsigned long long g_stamp[4 * 1024];
+#define TS_STAMP(slot) do { if (threadIdx.x == 0) g_stamp[(slot) * 1024 + blockIdx.x] = __builtin_readcyclecounter(); } while (0)
+#endif
 #include "../graph-neural-net_amd/csrc/tile_step_kernel.h"
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
 using namespace gnn;
+// (the head arguments: tile_step_kernel.h, GNN_TS_HEAD_PARAMS -- in this order)
+#define TSHEAD(p, hd) (p).layer[0].A, (p).layer[0].D, (p).layer[0].W, (p).layer[0].V, (p).layer[0].lda, (p).layer[0].ldd, (p).layer[0].M, ((p).K | ((p).row_idx ? 1 : 0)), (hd).geo, (hd).kx
+#define LAUNCH(kern, grid, p, hd) hipLaunchKernelGGL(kern, dim3(grid), dim3(TS_THREADS), 0, s, TSHEAD(p, hd), p)
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e)); exit(1);} } while (0)
 
 int main(int argc, char **argv) {
@@ -57,6 +69,9 @@ int main(int argc, char **argv) {
     tiles = (int)hm.size(); tiles0 = (int)hm0.size();
     t.tile_map = map_new;
     t.map_in_args = pack_tile_map(hm, t.map_words) ? 1 : 0;
+    // the regular slots' decode words of the two host-built maps; none for the rectangle grids and for the lines that time a lookup
+    const TileHead hd_all = make_tile_head(ml, hm), hd_first = make_tile_head(ml, hm0), hd_none{0, 0};
+    printf("head words: all layers %08x %08x, layer 0 alone %08x %08x\n", hd_all.geo, hd_all.kx, hd_first.geo, hd_first.kx);
     printf("tiles: %d (layer 0: %d) with the host-built map, %d (%d) with the rectangles of every layer; %d slabs\n", tiles, tiles0, tiles_old, tiles0_old, ns);
     hipStream_t s; CK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
     hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
@@ -71,19 +86,53 @@ int main(int argc, char **argv) {
     {
         TileStepParams o = t; o.tile_map = map_old; o.map_in_args = 0;
         TileStepParams tg = t; tg.map_in_args = 0; // the host-built map read from memory
-        time_it("tile_step<grad, update, fwd>, rectangles of every layer", 500, [&]() { hipLaunchKernelGGL((tile_step_kernel<1, 2, true>), dim3(tiles_old), dim3(TS_THREADS), 0, s, o); });
-        time_it("tile_step<grad, update, fwd>, host-built map in the kernel arguments", 500, [&]() { hipLaunchKernelGGL((tile_step_kernel<1, 2, true>), dim3(tiles), dim3(TS_THREADS), 0, s, t); });
-        time_it("tile_step<grad, update, fwd>, host-built map read from memory", 500, [&]() { hipLaunchKernelGGL((tile_step_kernel<1, 2, true>), dim3(tiles), dim3(TS_THREADS), 0, s, tg); });
-        time_it("tile_step<grad, update, fwd>, rectangles of every layer", 500, [&]() { hipLaunchKernelGGL((tile_step_kernel<1, 2, true>), dim3(tiles_old), dim3(TS_THREADS), 0, s, o); });
-        time_it("tile_step<grad, update, fwd>, host-built map in the kernel arguments", 500, [&]() { hipLaunchKernelGGL((tile_step_kernel<1, 2, true>), dim3(tiles), dim3(TS_THREADS), 0, s, t); });
-        time_it("tile_step<grad, update, fwd>, host-built map read from memory", 500, [&]() { hipLaunchKernelGGL((tile_step_kernel<1, 2, true>), dim3(tiles), dim3(TS_THREADS), 0, s, tg); });
+        time_it("tile_step<grad, update, fwd>, rectangles of every layer", 500, [&]() { LAUNCH((tile_step_kernel<1, 2, true>), tiles_old, o, hd_none); });
+        time_it("tile_step<grad, update, fwd>, host-built map in the kernel arguments", 500, [&]() { LAUNCH((tile_step_kernel<1, 2, true>), tiles, t, hd_all); });
+        time_it("tile_step<grad, update, fwd>, host-built map read from memory", 500, [&]() { LAUNCH((tile_step_kernel<1, 2, true>), tiles, tg, hd_none); });
+        time_it("tile_step<grad, update, fwd>, rectangles of every layer", 500, [&]() { LAUNCH((tile_step_kernel<1, 2, true>), tiles_old, o, hd_none); });
+        time_it("tile_step<grad, update, fwd>, host-built map in the kernel arguments", 500, [&]() { LAUNCH((tile_step_kernel<1, 2, true>), tiles, t, hd_all); });
+        time_it("tile_step<grad, update, fwd>, host-built map read from memory", 500, [&]() { LAUNCH((tile_step_kernel<1, 2, true>), tiles, tg, hd_none); });
         TileStepParams o0 = t; o0.n_layers = 1; o0.tile_map = map0_old; o0.map_in_args = 0;
         TileStepParams n0 = t; n0.n_layers = 1; n0.tile_map = map0_new; n0.map_in_args = pack_tile_map(hm0, n0.map_words) ? 1 : 0;
-        time_it("tile_step<fwd only>, rectangles", 500, [&]() { hipLaunchKernelGGL((tile_step_kernel<0, 0, true>), dim3(tiles0_old), dim3(TS_THREADS), 0, s, o0); });
-        time_it("tile_step<fwd only>, host-built map", 500, [&]() { hipLaunchKernelGGL((tile_step_kernel<0, 0, true>), dim3(tiles0), dim3(TS_THREADS), 0, s, n0); });
+        time_it("tile_step<fwd only>, rectangles", 500, [&]() { LAUNCH((tile_step_kernel<0, 0, true>), tiles0_old, o0, hd_none); });
+        time_it("tile_step<fwd only>, host-built map", 500, [&]() { LAUNCH((tile_step_kernel<0, 0, true>), tiles0, n0, hd_first); });
+    }
+    {   // the prologue variants of <grad, update, fwd> on the host-built map, three rounds in turn: the form before (arguments from the
+        // struct, every tile by lookup, W and V at the top), A (head arguments, regular slots decoded), B (W and V behind the first
+        // barrier), A + B.  A round's spread from the next is the probe's own noise.
+        for (int rep = 0; rep < 3; rep++) {
+            time_it("prologue: struct + lookup, W/V at the top (before)", 1000, [&]() { LAUNCH((tile_step_kernel<1, 2, true, false, false>), tiles, t, hd_all); });
+            time_it("prologue: A  head arguments + decoded tile", 1000, [&]() { LAUNCH((tile_step_kernel<1, 2, true, true, false>), tiles, t, hd_all); });
+            time_it("prologue: B  W/V behind the first barrier", 1000, [&]() { LAUNCH((tile_step_kernel<1, 2, true, false, true>), tiles, t, hd_all); });
+            time_it("prologue: A + B", 1000, [&]() { LAUNCH((tile_step_kernel<1, 2, true, true, true>), tiles, t, hd_all); });
+        }
+#ifdef TILE_PROBE_STAMPS
+        // stamps of the whole layer-0 tiles' workgroups (the heavy ones), cycles from the workgroup's own first stamp, mean and maximum
+        auto stamps = [&](const char *name, auto fn) {
+            fn(); CK(hipStreamSynchronize(s)); fn(); CK(hipStreamSynchronize(s));
+            std::vector<unsigned long long> st(4 * 1024);
+            CK(hipMemcpyFromSymbol(st.data(), HIP_SYMBOL(g_stamp), st.size() * 8));
+            double sum[4] = {0, 0, 0, 0}, mx[4] = {0, 0, 0, 0}; int n = 0;
+            auto whole = [&](int id) { return hm[id] != ~0u && (hm[id] & 15u) == 0 && (int)((hm[id] >> 4) & 0x3fffu) * TS_TM + TS_TM <= ld[0]; };
+            // (cycles from the workgroup's OWN first stamp: the counters of two CUs are not comparable)
+            for (int id = 0; id < tiles; id++) {
+                if (!whole(id)) continue;
+                n++;
+                for (int k = 1; k < 4; k++) { const double d = (double)(st[k * 1024 + id] - st[id]); sum[k] += d; mx[k] = d > mx[k] ? d : mx[k]; }
+            }
+            printf("stamps %-44s %d workgroups: first loads issued %6.0f (max %6.0f)  first barrier %6.0f (max %6.0f)  end %6.0f (max %6.0f) cycles\n",
+                   name, n, sum[1] / n, mx[1], sum[2] / n, mx[2], sum[3] / n, mx[3]);
+        };
+        for (int rep = 0; rep < 2; rep++) {
+            stamps("struct + lookup, W/V at the top (before)", [&]() { LAUNCH((tile_step_kernel<1, 2, true, false, false>), tiles, t, hd_all); });
+            stamps("A  head arguments + decoded tile", [&]() { LAUNCH((tile_step_kernel<1, 2, true, true, false>), tiles, t, hd_all); });
+            stamps("B  W/V behind the first barrier", [&]() { LAUNCH((tile_step_kernel<1, 2, true, false, true>), tiles, t, hd_all); });
+            stamps("A + B", [&]() { LAUNCH((tile_step_kernel<1, 2, true, true, true>), tiles, t, hd_all); });
+        }
+#endif
     }
     {   // a pair as in a real step: the tile kernel followed by a dependent small kernel (what the next launch waits for)
-        time_it("pair: tile_step + dependent fwd-only launch", 300, [&]() { hipLaunchKernelGGL((tile_step_kernel<1, 2, true>), dim3(tiles), dim3(TS_THREADS), 0, s, t); TileStepParams u = t; u.n_layers = 1; u.tile_map = map0_new; u.map_in_args = pack_tile_map(hm0, u.map_words) ? 1 : 0; hipLaunchKernelGGL((tile_step_kernel<0, 0, true>), dim3(tiles0), dim3(TS_THREADS), 0, s, u); });
+        time_it("pair: tile_step + dependent fwd-only launch", 300, [&]() { LAUNCH((tile_step_kernel<1, 2, true>), tiles, t, hd_all); TileStepParams u = t; u.n_layers = 1; u.tile_map = map0_new; u.map_in_args = pack_tile_map(hm0, u.map_words) ? 1 : 0; LAUNCH((tile_step_kernel<0, 0, true>), tiles0, u, hd_first); });
     }
     {   // a SAMPLED next batch: rows gathered through an index vector from a 6 000-row data set, with and without the contiguous copy
         const int NR = 6000;
@@ -95,14 +144,14 @@ int main(int argc, char **argv) {
         TileStepParams gc = g; gc.stage_out = copy;
         TileStepParams seq = t; seq.An = big; // the same data set, rows in place
         for (int rep = 0; rep < 2; rep++) {
-            time_it("next batch in place (6 000-row set)", 500, [&]() { hipLaunchKernelGGL((tile_step_kernel<1, 2, true>), dim3(tiles), dim3(TS_THREADS), 0, s, seq); });
-            time_it("next batch gathered by index", 500, [&]() { hipLaunchKernelGGL((tile_step_kernel<1, 2, true>), dim3(tiles), dim3(TS_THREADS), 0, s, g); });
-            time_it("next batch gathered + contiguous copy written", 500, [&]() { hipLaunchKernelGGL((tile_step_kernel<1, 2, true>), dim3(tiles), dim3(TS_THREADS), 0, s, gc); });
+            time_it("next batch in place (6 000-row set)", 500, [&]() { LAUNCH((tile_step_kernel<1, 2, true>), tiles, seq, hd_all); });
+            time_it("next batch gathered by index", 500, [&]() { LAUNCH((tile_step_kernel<1, 2, true>), tiles, g, hd_all); });
+            time_it("next batch gathered + contiguous copy written", 500, [&]() { LAUNCH((tile_step_kernel<1, 2, true>), tiles, gc, hd_all); });
         }
     }
-    time_it("tile_step<grad, update>", 500, [&]() { hipLaunchKernelGGL((tile_step_kernel<1, 2, false>), dim3(tiles), dim3(TS_THREADS), 0, s, t); });
-    time_it("tile_step<grad, store G>", 500, [&]() { hipLaunchKernelGGL((tile_step_kernel<1, 1, false>), dim3(tiles), dim3(TS_THREADS), 0, s, t); });
-    time_it("tile_step<G, update, fwd>", 500, [&]() { hipLaunchKernelGGL((tile_step_kernel<2, 2, true>), dim3(tiles), dim3(TS_THREADS), 0, s, t); });
-    time_it("tile_step<fwd only> (layer 0 tiles)", 500, [&]() { TileStepParams u = t; u.n_layers = 1; u.tile_map = map0_new; u.map_in_args = pack_tile_map(hm0, u.map_words) ? 1 : 0; hipLaunchKernelGGL((tile_step_kernel<0, 0, true>), dim3(tiles0), dim3(TS_THREADS), 0, s, u); });
+    time_it("tile_step<grad, update>", 500, [&]() { LAUNCH((tile_step_kernel<1, 2, false>), tiles, t, hd_all); });
+    time_it("tile_step<grad, store G>", 500, [&]() { LAUNCH((tile_step_kernel<1, 1, false>), tiles, t, hd_all); });
+    time_it("tile_step<G, update, fwd>", 500, [&]() { LAUNCH((tile_step_kernel<2, 2, true>), tiles, t, hd_all); });
+    time_it("tile_step<fwd only> (layer 0 tiles)", 500, [&]() { TileStepParams u = t; u.n_layers = 1; u.tile_map = map0_new; u.map_in_args = pack_tile_map(hm0, u.map_words) ? 1 : 0; LAUNCH((tile_step_kernel<0, 0, true>), tiles0, u, hd_first); });
     return 0;
 }
