@@ -1,6 +1,6 @@
 // tile_step_body.inc -- the body of tile_step_kernel (tile_step_kernel.h), included INSIDE the kernels that run it:
 // the single-net kernel and its grouped twin (group_kernels.h).  In scope: the kernel argument `p` (TileStepParams),
-// the template parameters GSRC / GDST / FWD, TS_HEAD_PROLOGUE / TS_HEAD / TS_DEFER_WV / TS_HAS_ROW_IDX (tile_step_kernel.h), and nine macros that say who the kernel works for:
+// the template parameters GSRC / GDST / FWD, TS_HEAD_PROLOGUE / TS_HEAD / TS_DEFER_WV / TS_LOOKUP1 / TS_HAS_ROW_IDX (tile_step_kernel.h), and nine macros that say who the kernel works for:
 // TS_BID (the workgroup's index in the tile map), TS_REL(ptr) (the net's copy of a pointer of `p`), TS_REL_LAYER(L) (the same
 // for a layer descriptor), TS_STEP_OVER_B and TS_MOMENTUM, and the four row counts TS_K / TS_K_TRUE (the current batch, padded /
 // live) and TS_NEXT_K / TS_NEXT_ROWS (the next one).  The single-net kernels define them as the plain expressions
@@ -28,9 +28,38 @@
     // everything its first vector loads and the `interior` test need from the preloaded head arguments: no scalar load
     // stands in front of them.  Of the struct's descriptor only G is read then (the forms that store or fetch a gradient).
     const bool regular = TS_HEAD && ts_head_tile(hd_geo, hd_kx, (int)TS_BID, tm, tn); // (block-uniform)
+    bool have_L = false; // the descriptor of a later layer's tile is in L already
     if (regular) {
         li = 0;
         L.A = hd_A; L.D = hd_D; L.W = hd_W; L.V = hd_V; L.lda = hd_lda; L.ldd = hd_ldd; L.M = hd_M;
+    } else if (TS_HEAD && TS_LOOKUP1) {
+        // A slot that keeps the lookup (a later layer's tile, layer 0's partial last tile row) had up to four DEPENDENT scalar
+        // round trips in front of its first vector load: map_in_args, then the map word, then -- twice, the compiler waits
+        // between two loads into registers still in flight -- the descriptor the word names.  Here everything such a slot can
+        // need is requested in ONE batch: the flag, the word of this workgroup (its index clamped into the struct: the flag may
+        // say that the map is not there) and layer 1's descriptor (inside the struct whatever n_layers is); layer 0's is the head arguments' in every
+        // slot.  Only a tile of layer 2 or later, or a map that does not fit the arguments, pays a second trip.
+        const unsigned wi = (unsigned)(TS_BID >> 1) < (unsigned)(TS_MAP_ARGS / 2) ? (unsigned)(TS_BID >> 1) : (unsigned)(TS_MAP_ARGS / 2 - 1); // (clamped: a grid the words do not hold reads the table below)
+        const uint32_t w = p.map_words[wi];
+        const int in_args = p.map_in_args;
+        GradLayer L1 = p.layer[1];
+        // (an empty statement that "reads" them: left alone, the compiler sinks the descriptor's loads into the branch that
+        //  uses them, behind the wait for the word -- the second trip again)
+        asm volatile("" ::"s"(w), "s"(in_args), "s"(L1.A), "s"(L1.D), "s"(L1.W), "s"(L1.V), "s"(L1.lda), "s"(L1.ldd), "s"(L1.M));
+        if (GSRC >= 2 || GDST == 1) asm volatile("" ::"s"(L1.G));
+        uint32_t e = (TS_BID & 1) ? w >> 16 : w & 0xffffu;
+        li = (int)(e & 7u); tm = (int)((e >> 3) & 63u); tn = (int)(e >> 9);
+        bool idle = e == 0xffffu;
+        if (!in_args) {
+            e = p.tile_map[TS_BID];
+            idle = e == ~0u;
+            li = (int)(e & 15u); tm = (int)((e >> 4) & 0x3fffu); tn = (int)(e >> 18);
+        }
+        if (idle) return;
+        L.A = hd_A; L.D = hd_D; L.W = hd_W; L.V = hd_V; L.lda = hd_lda; L.ldd = hd_ldd; L.M = hd_M;
+        if (li == 1) L = L1;
+        else if (li != 0) L = p.layer[li];
+        have_L = true;
     } else
 #endif
     if (p.map_in_args) {
@@ -42,7 +71,11 @@
         if (e == ~0u) return;
         li = (int)(e & 15u); tm = (int)((e >> 4) & 0x3fffu); tn = (int)(e >> 18);
     }
+#if TS_HEAD_PROLOGUE
+    if (li != 0 && !have_L) L = p.layer[li];
+#else
     if (li != 0) L = p.layer[li];
+#endif
     TS_REL_LAYER(L);
     const int m0 = tm * TS_TM, n0 = tn * TS_TN;
     const bool fwd = FWD && li == 0; // block-uniform

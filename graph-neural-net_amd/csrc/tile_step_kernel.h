@@ -168,7 +168,9 @@ inline bool pack_tile_map(const std::vector<uint32_t> &map, uint32_t (&words)[TS
 // heavy ones, 228 of 284 on 784-300-100-10 -- forms the addresses of its first vector loads with no scalar load at all:
 //   geo = rm | rn << 6 | xs << 14 | full_m << 16 | tiles_n << 23   (the rectangles of make_xcd_tiling(full_m, tiles_n))
 //   kx  = k_x, four bits per XCD
-// Every other slot (the pair slots, the small layers, a partial last tile row, idle entries) keeps the lookup.  The MAP
+// Every other slot (the pair slots, the small layers, a partial last tile row, idle entries) keeps the lookup -- on the kernels
+// with the head prologue as ONE batch of scalar loads (tile_step_body.inc, TS_LOOKUP1: the flag, the map word, layer 1's
+// descriptor; layer 0's descriptor from the head arguments), not one dependent round trip after the other.  The MAP
 // stays the truth: make_tile_head evaluates the decode for every slot and hands out {0, 0} -- no regular slot -- unless
 // each slot the decode claims names exactly its map entry.
 struct TileHead { uint32_t geo, kx; };
@@ -267,11 +269,13 @@ template <int GSRC> __device__ __forceinline__ float4 ts_gradient_in(const TileS
 // kernel-argument line nothing had touched, in front of the first vector load.  Everything else -- what the forward half
 // needs behind the barrier included -- stays in the struct; so does the descriptor of every slot that is not regular.
 // HEAD = false (GNN_MLP_TILE_HEAD=0): the prologue as it was, every argument from the struct and every tile from the
-// lookup -- the reference point of the bitwise test.  DEFER_WV: tile_step_body.inc.  A launch passes the head, then p.
+// lookup -- the reference point of the bitwise test.  DEFER_WV, LOOKUP1 (off only in tools/tile_probe's comparisons): tile_step_body.inc.
+// A launch passes the head, then p.
 #define GNN_TS_HEAD_PARAMS const float *hd_A, const float *hd_D, float *hd_W, float *hd_V, int hd_lda, int hd_ldd, int hd_M, int hd_Kr, uint32_t hd_geo, uint32_t hd_kx
 #define TS_HEAD_PROLOGUE 1
 #define TS_HEAD HEAD
 #define TS_DEFER_WV DEFER_WV
+#define TS_LOOKUP1 LOOKUP1
 #ifndef TS_STAMP
 #define TS_STAMP(slot) // (tools/tile_probe.hip defines it in its stamped build; nothing is stamped in the library)
 #endif
@@ -286,7 +290,7 @@ template <int GSRC> __device__ __forceinline__ float4 ts_gradient_in(const TileS
 #define TS_STAGE_N p.layer[0].N // (layer 0's N where it is used, behind the barrier: as a field of L its scalar load was waited for at the top)
 #define TS_NEXT_ROWS p.next_rows
 #define TS_NEXT_K p.next_K
-template <int GSRC, int GDST, bool FWD, bool HEAD = true, bool DEFER_WV = true>
+template <int GSRC, int GDST, bool FWD, bool HEAD = true, bool DEFER_WV = true, bool LOOKUP1 = HEAD>
 __global__ __launch_bounds__(TS_THREADS) void tile_step_kernel(GNN_TS_HEAD_PARAMS, TileStepParams p) {
 #include "tile_step_body.inc"
 }
@@ -307,6 +311,7 @@ __global__ __launch_bounds__(TS_THREADS) void tile_step_bf16_kernel(GNN_TS_HEAD_
 #undef TS_HEAD_PROLOGUE
 #undef TS_HEAD
 #undef TS_DEFER_WV
+#undef TS_LOOKUP1
 #undef TS_HAS_ROW_IDX
 #undef TS_STAGE_N
 #undef TS_BID

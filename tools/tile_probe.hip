@@ -7,7 +7,13 @@
 #ifdef TILE_PROBE_STAMPS
 #include <hip/hip_runtime.h>
 __device__ unsigned long long g_stamp[4 * 1024];
-#define TS_STAMP(slot) do { if (threadIdx.x == 0) g_stamp[(slot) * 1024 + blockIdx.x] = __builtin_readcyclecounter(); } while (0)
+// the first and the last of them also on the 100 MHz real-time counter, which every CU reads alike (the cycle counters of two CUs are not
+// comparable), and where the workgroup ran: HW_ID (CU, shader array and engine in bits 8..15) and the XCC id
+__device__ unsigned long long g_real[4 * 1024];
+__device__ unsigned g_where[2 * 1024];
+#define TS_STAMP(slot) do { if (threadIdx.x == 0) { g_stamp[(slot) * 1024 + blockIdx.x] = __builtin_readcyclecounter(); \
+    if ((slot) == 0 || (slot) == 3) g_real[(slot) * 1024 + blockIdx.x] = __builtin_amdgcn_s_memrealtime(); \
+    if ((slot) == 3) { g_where[blockIdx.x] = (unsigned)__builtin_amdgcn_s_getreg(0xF804); g_where[1024 + blockIdx.x] = (unsigned)__builtin_amdgcn_s_getreg(0xF814) & 15u; } } } while (0)
 #endif
 #include "../graph-neural-net_amd/csrc/tile_step_kernel.h"
 #include <cstdio>
@@ -99,12 +105,38 @@ int main(int argc, char **argv) {
     }
     {   // the prologue variants of <grad, update, fwd> on the host-built map, three rounds in turn: the form before (arguments from the
         // struct, every tile by lookup, W and V at the top), A (head arguments, regular slots decoded), B (W and V behind the first
-        // barrier), A + B.  A round's spread from the next is the probe's own noise.
+        // barrier), A + B, and A + B + C (the slots that keep the lookup ask for all they need in one batch of scalar loads: the library's kernel).  A round's spread from the next is the probe's own noise.
         for (int rep = 0; rep < 3; rep++) {
-            time_it("prologue: struct + lookup, W/V at the top (before)", 1000, [&]() { LAUNCH((tile_step_kernel<1, 2, true, false, false>), tiles, t, hd_all); });
-            time_it("prologue: A  head arguments + decoded tile", 1000, [&]() { LAUNCH((tile_step_kernel<1, 2, true, true, false>), tiles, t, hd_all); });
-            time_it("prologue: B  W/V behind the first barrier", 1000, [&]() { LAUNCH((tile_step_kernel<1, 2, true, false, true>), tiles, t, hd_all); });
-            time_it("prologue: A + B", 1000, [&]() { LAUNCH((tile_step_kernel<1, 2, true, true, true>), tiles, t, hd_all); });
+            time_it("prologue: struct + lookup, W/V at the top (before)", 1000, [&]() { LAUNCH((tile_step_kernel<1, 2, true, false, false, false>), tiles, t, hd_all); });
+            time_it("prologue: A  head arguments + decoded tile", 1000, [&]() { LAUNCH((tile_step_kernel<1, 2, true, true, false, false>), tiles, t, hd_all); });
+            time_it("prologue: B  W/V behind the first barrier", 1000, [&]() { LAUNCH((tile_step_kernel<1, 2, true, false, true, false>), tiles, t, hd_all); });
+            time_it("prologue: A + B", 1000, [&]() { LAUNCH((tile_step_kernel<1, 2, true, true, true, false>), tiles, t, hd_all); });
+            time_it("prologue: A + B + C  lookup slots in one scalar batch", 1000, [&]() { LAUNCH((tile_step_kernel<1, 2, true, true, true, true>), tiles, t, hd_all); });
+        }
+        // Upper bounds, before anything is built: the same launch with one class of workgroups TAKEN OUT of the map (idle entries:
+        // the workgroup returns at its top, its tile is not computed).  What a class can give back at most by becoming lighter
+        // is what the kernel gains when it is not there at all.
+        //   no partial row: layer 0's partial last tile row (19 tiles of 16 weights rows on 784-300-100-10)
+        //   no partner of a whole tile: the later-layer tiles in the slots that share a CU with a WHOLE layer-0 tile (slot j and
+        //   slot j + 8 * 32 share one)
+        auto is_whole = [&](uint32_t e) { return e != ~0u && (e & 15u) == 0 && (int)((e >> 4) & 0x3fffu) * TS_TM + TS_TM <= ld[0]; };
+        std::vector<uint32_t> hm_nopart = hm, hm_nopartner = hm;
+        int n_part = 0, n_partner = 0;
+        for (size_t id = 0; id < hm.size(); id++) {
+            if (hm[id] != ~0u && (hm[id] & 15u) == 0 && !is_whole(hm[id])) { hm_nopart[id] = ~0u; n_part++; }
+            if (id >= 256 && hm[id] != ~0u && (hm[id] & 15u) != 0 && is_whole(hm[id - 256])) { hm_nopartner[id] = ~0u; n_partner++; }
+        }
+        TileStepParams t_nopart = t, t_nopartner = t;
+        t_nopart.tile_map = to_dev(hm_nopart); t_nopart.map_in_args = pack_tile_map(hm_nopart, t_nopart.map_words) ? 1 : 0;
+        t_nopartner.tile_map = to_dev(hm_nopartner); t_nopartner.map_in_args = pack_tile_map(hm_nopartner, t_nopartner.map_words) ? 1 : 0;
+        printf("bounds: %d partial-row tiles, %d later-layer tiles that share a CU with a whole layer-0 tile\n", n_part, n_partner);
+        for (int rep = 0; rep < 3; rep++) {
+            time_it("bound: every tile (A + B)", 1000, [&]() { LAUNCH((tile_step_kernel<1, 2, true, true, true, false>), tiles, t, hd_all); });
+            time_it("bound: no partial row", 1000, [&]() { LAUNCH((tile_step_kernel<1, 2, true, true, true, false>), tiles, t_nopart, hd_all); });
+            time_it("bound: no partner of a whole tile", 1000, [&]() { LAUNCH((tile_step_kernel<1, 2, true, true, true, false>), tiles, t_nopartner, hd_all); });
+            time_it("bound: every tile (A + B + C)", 1000, [&]() { LAUNCH((tile_step_kernel<1, 2, true, true, true, true>), tiles, t, hd_all); });
+            time_it("bound: no partial row (A + B + C)", 1000, [&]() { LAUNCH((tile_step_kernel<1, 2, true, true, true, true>), tiles, t_nopart, hd_all); });
+            time_it("bound: no partner of a whole tile (A + B + C)", 1000, [&]() { LAUNCH((tile_step_kernel<1, 2, true, true, true, true>), tiles, t_nopartner, hd_all); });
         }
 #ifdef TILE_PROBE_STAMPS
         // stamps of the whole layer-0 tiles' workgroups (the heavy ones), cycles from the workgroup's own first stamp, mean and maximum
@@ -123,11 +155,70 @@ int main(int argc, char **argv) {
             printf("stamps %-44s %d workgroups: first loads issued %6.0f (max %6.0f)  first barrier %6.0f (max %6.0f)  end %6.0f (max %6.0f) cycles\n",
                    name, n, sum[1] / n, mx[1], sum[2] / n, mx[2], sum[3] / n, mx[3]);
         };
+        // The same workgroups by CLASS -- a whole layer-0 tile (regular), a tile of layer 0's partial last tile row, a tile of a
+        // later layer; each alone on its CU or sharing it with another workgroup of this launch -- on the clock that is
+        // comparable across CUs: start and end in us from the launch's first start (10-ns ticks), and which class holds the
+        // kernel's last end.  The three cycle stamps are from the workgroup's own first stamp, as above.
+        auto classes = [&](const char *name, const std::vector<uint32_t> &hm, auto fn) {
+            fn(); CK(hipStreamSynchronize(s)); fn(); CK(hipStreamSynchronize(s));
+            std::vector<unsigned long long> st(4 * 1024), rt(4 * 1024); std::vector<unsigned> wh(2 * 1024);
+            CK(hipMemcpyFromSymbol(st.data(), HIP_SYMBOL(g_stamp), st.size() * 8));
+            CK(hipMemcpyFromSymbol(rt.data(), HIP_SYMBOL(g_real), rt.size() * 8));
+            CK(hipMemcpyFromSymbol(wh.data(), HIP_SYMBOL(g_where), wh.size() * 4));
+            auto cu_of = [&](int id) { return wh[1024 + id] << 8 | ((wh[id] >> 8) & 0xffu); };
+            std::vector<int> on_cu(16 * 256, 0);
+            unsigned long long first = ~0ull;
+            for (int id = 0; id < tiles; id++) if (hm[id] != ~0u) { on_cu[cu_of(id)]++; first = rt[id] < first ? rt[id] : first; }
+            static const char *cname[3] = {"whole layer-0 tile (regular)", "partial last row of layer 0", "tile of a later layer"};
+            struct C { int n = 0; double start = 0, end = 0, last = 0, cyc[4] = {0, 0, 0, 0}; int last_id = -1; } c[3][2];
+            double kernel_end = 0; int end_cls = 0, end_sh = 0, end_id = -1;
+            for (int id = 0; id < tiles; id++) {
+                if (hm[id] == ~0u) continue;
+                const int li = (int)(hm[id] & 15u), tm = (int)((hm[id] >> 4) & 0x3fffu);
+                const int cls = li != 0 ? 2 : (tm * TS_TM + TS_TM <= ld[0] ? 0 : 1), sh = on_cu[cu_of(id)] > 1 ? 1 : 0;
+                C &k = c[cls][sh];
+                const double b = (double)(rt[id] - first) * 0.01, e = (double)(rt[3 * 1024 + id] - first) * 0.01;
+                k.n++; k.start += b; k.end += e;
+                if (e > k.last) { k.last = e; k.last_id = id; }
+                for (int q = 1; q < 4; q++) k.cyc[q] += (double)(st[q * 1024 + id] - st[id]);
+                if (e > kernel_end) { kernel_end = e; end_cls = cls; end_sh = sh; end_id = id; }
+            }
+            printf("classes %s\n", name);
+            for (int cls = 0; cls < 3; cls++) for (int sh = 0; sh < 2; sh++) {
+                const C &k = c[cls][sh];
+                if (!k.n) continue;
+                printf("  %-30s %-8s %3d workgroups: start +%.2f  end mean +%.2f  latest +%.2f (wg%d) us | first loads issued %6.0f  first barrier %6.0f  end %6.0f cycles\n",
+                       cname[cls], sh ? "sharing" : "alone", k.n, k.start / k.n, k.end / k.n, k.last, k.last_id, k.cyc[1] / k.n, k.cyc[2] / k.n, k.cyc[3] / k.n);
+            }
+            printf("  the kernel's last end: +%.2f us, wg%d, %s, %s\n", kernel_end, end_id, cname[end_cls], end_sh ? "sharing its CU" : "alone on its CU");
+            return std::vector<unsigned long long>(rt);
+        };
+        auto pairs = [&](const char *name, const std::vector<uint32_t> &hm, auto fn) { // every CU with two workgroups: [start, end] of each, us from the first start
+            const std::vector<unsigned long long> rt = classes(name, hm, fn);
+            std::vector<unsigned> wh(2 * 1024);
+            CK(hipMemcpyFromSymbol(wh.data(), HIP_SYMBOL(g_where), wh.size() * 4));
+            unsigned long long first = ~0ull;
+            for (int id = 0; id < tiles; id++) if (hm[id] != ~0u) first = rt[id] < first ? rt[id] : first;
+            for (int a = 0; a < tiles; a++) for (int b = a + 1; b < tiles; b++) {
+                if (hm[a] == ~0u || hm[b] == ~0u || wh[1024 + a] != wh[1024 + b] || ((wh[a] ^ wh[b]) & 0xff00u)) continue;
+                auto show = [&](int id) { printf("  wg%-3d layer %u row %2u [+%.2f, +%.2f]", id, hm[id] & 15u, (hm[id] >> 4) & 0x3fffu, (double)(rt[id] - first) * 0.01, (double)(rt[3 * 1024 + id] - first) * 0.01); };
+                printf("  xcc %u cu %02x:", wh[1024 + a], (wh[a] >> 8) & 0xffu); show(a); show(b); printf("\n");
+            }
+        };
+        for (int rep = 0; rep < 3; rep++) {
+            classes("A + B", hm, [&]() { LAUNCH((tile_step_kernel<1, 2, true, true, true, false>), tiles, t, hd_all); });
+            classes("A + B + C (the library's kernel)", hm, [&]() { LAUNCH((tile_step_kernel<1, 2, true, true, true, true>), tiles, t, hd_all); });
+        }
+        pairs("A + B, with the CUs that hold two workgroups", hm, [&]() { LAUNCH((tile_step_kernel<1, 2, true, true, true, false>), tiles, t, hd_all); });
+        pairs("A + B + C (the library's kernel), with the CUs that hold two workgroups", hm, [&]() { LAUNCH((tile_step_kernel<1, 2, true, true, true, true>), tiles, t, hd_all); });
+        classes("bound: no partial row", hm_nopart, [&]() { LAUNCH((tile_step_kernel<1, 2, true, true, true, false>), tiles, t_nopart, hd_all); });
+        classes("bound: no partner of a whole tile", hm_nopartner, [&]() { LAUNCH((tile_step_kernel<1, 2, true, true, true, false>), tiles, t_nopartner, hd_all); });
         for (int rep = 0; rep < 2; rep++) {
-            stamps("struct + lookup, W/V at the top (before)", [&]() { LAUNCH((tile_step_kernel<1, 2, true, false, false>), tiles, t, hd_all); });
-            stamps("A  head arguments + decoded tile", [&]() { LAUNCH((tile_step_kernel<1, 2, true, true, false>), tiles, t, hd_all); });
-            stamps("B  W/V behind the first barrier", [&]() { LAUNCH((tile_step_kernel<1, 2, true, false, true>), tiles, t, hd_all); });
-            stamps("A + B", [&]() { LAUNCH((tile_step_kernel<1, 2, true, true, true>), tiles, t, hd_all); });
+            stamps("struct + lookup, W/V at the top (before)", [&]() { LAUNCH((tile_step_kernel<1, 2, true, false, false, false>), tiles, t, hd_all); });
+            stamps("A  head arguments + decoded tile", [&]() { LAUNCH((tile_step_kernel<1, 2, true, true, false, false>), tiles, t, hd_all); });
+            stamps("B  W/V behind the first barrier", [&]() { LAUNCH((tile_step_kernel<1, 2, true, false, true, false>), tiles, t, hd_all); });
+            stamps("A + B", [&]() { LAUNCH((tile_step_kernel<1, 2, true, true, true, false>), tiles, t, hd_all); });
+            stamps("A + B + C", [&]() { LAUNCH((tile_step_kernel<1, 2, true, true, true, true>), tiles, t, hd_all); });
         }
 #endif
     }
