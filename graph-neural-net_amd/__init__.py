@@ -14,4 +14,4 @@ from .neural_net import (  # noqa: F401
     LOSS_HALF_SQUARED, OUT_ACT_LOSS, OUT_SOFTMAX_CE, REDUCE_DIRECT, REDUCE_DIRECT_RS, REDUCE_RCCL, DataParallelNeuralNet, GeneralNeuralNet,
     NetGroup, NeuralNet, SoftmaxCrossEntropyNeuralNet)
 from .trainer import (  # noqa: F401
-    NetGroupTrainer, NeuralNetTrainer, Sampler, accuracy, log_test, per_class, read_idx_images, read_idx_labels, train_log_row)
+    NetGroupTrainer, NeuralNetTrainer, Sampler, accuracy, fgsm, log_test, per_class, read_idx_images, read_idx_labels, train_log_row)

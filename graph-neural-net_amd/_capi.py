@@ -50,6 +50,8 @@ SYMBOLS = [
     ("gnn_mlp_argmax_range", C.c_int, [_H, C.c_int64, C.c_int, _ip]),
     ("gnn_mlp_count_hits_range", C.c_int, [_H, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
     ("gnn_mlp_evaluate_range", C.c_int, [_H, C.c_int64, C.c_int64, C.POINTER(C.c_int64), _dp, C.POINTER(C.c_int64), _ip]),
+    ("gnn_mlp_input_gradient", C.c_int, [_H, _dp, _dp, C.c_int, _dp]),
+    ("gnn_mlp_input_gradient_range", C.c_int, [_H, C.c_int64, C.c_int64, _dp, _dp, C.POINTER(C.c_int64)]),
     ("gnn_sampler_create", C.c_int, [C.c_int32, C.c_int64, C.POINTER(_H)]),
     ("gnn_sampler_destroy", C.c_int, [_H]),
     ("gnn_sampler_sample", C.c_int, [_H, C.c_int, _ip, C.POINTER(C.c_int)]),
@@ -98,6 +100,7 @@ SYMBOLS = [
     ("gnn_mlp_group_evaluate_range", C.c_int, [_H, C.c_int64, C.c_int64, C.POINTER(C.c_int64), _dp, C.POINTER(C.c_int64)]),
     ("gnn_mlp_group_ensemble_range", C.c_int, [_H, C.c_int64, C.c_int64, _dp, _ip]),
     ("gnn_mlp_group_confusion_range", C.c_int, [_H, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _ip]),
+    ("gnn_mlp_group_input_gradient_range", C.c_int, [_H, C.c_int64, C.c_int64, _dp, _dp, _dp, _dp, C.POINTER(C.c_int64)]),
     ("gnn_mlp_forget_lookahead", C.c_int, [_H]),
     ("gnn_mlp_advance_time", C.c_int, [_H, C.c_int]),
     ("gnn_mlp_recover_stream", C.c_int, [_H]),

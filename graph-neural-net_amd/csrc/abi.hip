@@ -278,7 +278,7 @@ void destroy_handle(gnn_mlp *h) {
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     rccl_detach_handle(h);
     auto fr = [h](void *p) { dev_release(h, p); };
-    fr(h->W); fr(h->V); fr(h->G_own); fr(h->act0_alt); free_eval_workspace(h);
+    fr(h->W); fr(h->V); fr(h->G_own); fr(h->act0_alt); free_eval_workspace(h); free_input_grad(h);
     for (float *p : h->act) fr(p);
     for (float *p : h->delta) fr(p);
     fr(h->logits); fr(h->prob); fr(h->ybuf); fr(h->lossv); fr(h->labels); fr(h->idxbuf);

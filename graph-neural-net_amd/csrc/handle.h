@@ -155,6 +155,9 @@ struct gnn_mlp {
         float *logits = nullptr, *prob = nullptr, *lossv = nullptr;
         int32_t *labels = nullptr;
     } evalws;
+    // the input gradient of the block last run through input_grad.hip: pad(max_batch) x ld[0], made on first use, never a slice
+    // of a group's arena
+    float *gx = nullptr;
 
     // one process per GPU with the exchange inside the library's step loop (gnn_mlp_rccl_*, dp.hip): this rank's communicator
     void *rccl_comm = nullptr; int rccl_ranks = 0, rccl_rank = 0;
@@ -433,6 +436,7 @@ struct EvalScope { // for blocks above max_batch: the evaluation workspace's buf
     void swap();
 };
 void free_eval_workspace(gnn_mlp *h);
+void free_input_grad(gnn_mlp *h); // (input_grad.hip; destroy_handle calls it)
 void rccl_detach_handle(gnn_mlp *h); // (dp.hip; gnn_mlp_destroy calls it)
 bool can_defer_update(const gnn_mlp *h);
 int step_on_host_batch_deferred(gnn_mlp *h, int B, double step, double momentum); // act[0] / ybuf hold the staged batch

@@ -1,0 +1,209 @@
+// input_grad.hip -- the gradient of calculateLoss with respect to the INPUT (NN:27, SCE:207-220, GNN:230-242): host side of
+// input_grad_kernel.h.  Per block of at most max_batch rows: the handle's own gradient computation without an update
+// (do_gradient, untouched: every plan leaves delta_1 -- bf16 nets its rounding deltab[1] -- on the device), one launch of
+// input_grad_kernel into the handle's gx buffer, then the consumers (saliency_kernel, a device-to-device copy of the rows, for
+// groups input_grad_combine_kernel).  No host work between blocks; the results come back in ONE readback at the end of a call.
+// Like gnn_mlp_compute_gradient*, a call leaves the gradient buffer holding its last block's weight gradient; it changes no
+// weight, momentum, step count or sampler.
+#include "handle.h"
+#include "input_grad_kernel.h"
+
+#include <algorithm>
+
+using namespace gnn;
+using namespace gnn::host;
+
+static_assert(IG_GROUP_MAX == GROUP_MAX, "input_grad_kernel.h and group_kernels.h: one member count");
+
+namespace {
+
+// gx: pad(max_batch) x ld[0] floats, an ordinary allocation (never a slice of a group's arena), made on first use
+int ensure_gx(gnn_mlp *h) {
+    if (h->gx) return GNN_OK;
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&h->gx), sizeof(float) * (size_t)h->cap_rows * h->ld[0]));
+    return GNN_OK;
+}
+
+// gx = (delta_1 . W_0^T) * f'(a0) of the block do_gradient has just run on
+void enqueue_input_grad(gnn_mlp *h, const float *a0, int B) {
+    const bool bf = h->dtype == GNN_DTYPE_BF16;
+    InputGradParams p{};
+    p.D = bf ? static_cast<const void *>(h->deltab[1]) : static_cast<const void *>(h->delta[1]);
+    p.W = bf ? static_cast<const void *>(h->Wb + h->w_off[0]) : static_cast<const void *>(h->W + h->w_off[0]);
+    p.A0 = a0; p.lda = h->ld[0];
+    p.GX = h->gx; p.ldg = h->ld[0];
+    p.M = h->ld[0]; p.m_true = h->dims[0];
+    p.K = h->ld[1];
+    p.rows = B;
+    p.act = h->inner_act;
+    const dim3 grid((unsigned)((h->ld[0] / 16 + IG_WAVES - 1) / IG_WAVES), (unsigned)(pad_up(B) / 16));
+    if (bf) hipLaunchKernelGGL(input_grad_kernel<true>, grid, dim3(IG_WAVES * 64), 0, h->stream, p);
+    else hipLaunchKernelGGL(input_grad_kernel<false>, grid, dim3(IG_WAVES * 64), 0, h->stream, p);
+}
+
+// sal[c][i] += |gx[b][i]| over the block's rows of class c, class_rows[c] += their number (either may be null, not both)
+void enqueue_saliency(const gnn_mlp *h, hipStream_t stream, const float *gx, const float *y, int B, double *sal,
+                      unsigned long long *class_rows) {
+    const int Lm = h->L - 1;
+    SaliencyParams s{};
+    s.GX = gx; s.ldg = h->ld[0];
+    s.d0 = h->dims[0]; s.rows = B; s.n_out = h->dims[Lm];
+    s.Y = y; s.ldy = h->ld[Lm];
+    s.sal = sal; s.class_rows = class_rows;
+    const unsigned gx_blocks = sal ? (unsigned)((h->dims[0] + SAL_NT - 1) / SAL_NT) : 1u;
+    hipLaunchKernelGGL(saliency_kernel, dim3(gx_blocks, (unsigned)h->dims[Lm]), dim3(SAL_NT), 0, stream, s);
+}
+
+// the block's live rows without their padding, behind the rows of the blocks before it
+int enqueue_row_copy(const gnn_mlp *h, hipStream_t stream, const float *gx, int B, float *dst) {
+    const size_t w = sizeof(float) * (size_t)h->dims[0];
+    HIP_TRY(hipMemcpy2DAsync(dst, w, gx, sizeof(float) * (size_t)h->ld[0], w, (size_t)B, hipMemcpyDeviceToDevice, stream));
+    return GNN_OK;
+}
+
+int check_rows(const gnn_mlp *h, int64_t first, int64_t n) {
+    if (!h->DX) return fail(GNN_ERR_STATE, "no dataset uploaded");
+    if (n <= 0 || first < 0 || first + n > h->dataset_n) return fail(GNN_ERR_BAD_ARG, "rows outside the dataset");
+    return GNN_OK;
+}
+
+void widen(const float *src, double *dst, size_t n) {
+    for (size_t i = 0; i < n; i++) dst[i] = (double)src[i];
+}
+
+} // namespace
+
+namespace gnn {
+namespace host {
+void free_input_grad(gnn_mlp *h) {
+    if (h->gx) (void)hipFree(h->gx);
+    h->gx = nullptr;
+}
+} // namespace host
+} // namespace gnn
+
+extern "C" {
+
+int gnn_mlp_input_gradient(gnn_mlp_t *h, const double *X, const double *Y, int B, double *grad) { return guarded([&]() -> int {
+    TRY(check_handle(h));
+    if (!X || !Y || !grad) return fail(GNN_ERR_BAD_ARG, "null argument (SCE:209)");
+    TRY(check_batch(h, B));
+    TRY(ensure_gx(h));
+    TRY(stage_batch(h, X, Y, B));
+    do_gradient(h, h->act[0], h->ybuf, B, false, 0.f, 0.f, false);
+    enqueue_input_grad(h, h->act[0], B);
+    TRY_LAUNCHES(h);
+    const int d0 = h->dims[0], ld0 = h->ld[0];
+    std::vector<float> host((size_t)B * ld0);
+    HIP_TRY(hipMemcpyAsync(host.data(), h->gx, sizeof(float) * host.size(), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    for (int b = 0; b < B; b++) widen(host.data() + (size_t)b * ld0, grad + (size_t)b * d0, (size_t)d0);
+    return GNN_OK;
+}); }
+
+int gnn_mlp_input_gradient_range(gnn_mlp_t *h, int64_t first, int64_t n, double *grad, double *saliency, int64_t *class_rows) {
+return guarded([&]() -> int {
+    TRY(check_handle(h));
+    if (!grad && !saliency && !class_rows) return fail(GNN_ERR_BAD_ARG, "every output is null");
+    TRY(check_rows(h, first, n));
+    TRY(ensure_gx(h));
+    const int Lm = h->L - 1, d0 = h->dims[0], d_out = h->dims[Lm];
+    // [d_out x d0 sums][d_out row counts] (one fill) | the rows' gradients without padding: one readback
+    const size_t cells = (size_t)d_out * d0;
+    static_assert(sizeof(unsigned long long) == sizeof(double), "one buffer for sums and counters");
+    const size_t head = sizeof(double) * (cells + (size_t)d_out), grad_b = grad ? sizeof(float) * (size_t)n * d0 : 0;
+    DevScratch res;
+    TRY(res.alloc(head + grad_b));
+    HIP_TRY(hipMemsetAsync(res.p, 0, head, h->stream));
+    double *d_sal = res.as<double>();
+    unsigned long long *d_rows = reinterpret_cast<unsigned long long *>(d_sal + cells);
+    float *d_grad = reinterpret_cast<float *>(res.as<char>() + head);
+    const int block = h->max_batch;
+    for (int64_t off = 0; off < n; off += block) {
+        const int B = (int)std::min<int64_t>(block, n - off);
+        const float *a0 = h->DX + (size_t)(first + off) * h->ld[0];
+        const float *y = h->DY + (size_t)(first + off) * h->ld[Lm];
+        do_gradient(h, a0, y, B, false, 0.f, 0.f, true);
+        enqueue_input_grad(h, a0, B);
+        if (saliency || class_rows) enqueue_saliency(h, h->stream, h->gx, y, B, saliency ? d_sal : nullptr, class_rows ? d_rows : nullptr);
+        if (grad) TRY(enqueue_row_copy(h, h->stream, h->gx, B, d_grad + (size_t)off * d0));
+    }
+    TRY_LAUNCHES(h);
+    std::vector<double> host((head + grad_b + 7) / 8);
+    HIP_TRY(hipMemcpyAsync(host.data(), res.p, head + grad_b, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (saliency) std::memcpy(saliency, host.data(), sizeof(double) * cells);
+    if (class_rows) {
+        const unsigned long long *c = reinterpret_cast<const unsigned long long *>(host.data() + cells);
+        for (int i = 0; i < d_out; i++) class_rows[i] = (int64_t)c[i];
+    }
+    if (grad) widen(reinterpret_cast<const float *>(reinterpret_cast<const char *>(host.data()) + head), grad, (size_t)n * d0);
+    return GNN_OK;
+}); }
+
+int gnn_mlp_group_input_gradient_range(gnn_mlp_group_t *g, int64_t first, int64_t n, double *member_grad, double *ensemble_grad,
+                                       double *member_saliency, double *ensemble_saliency, int64_t *class_rows) {
+return guarded([&]() -> int {
+    if (!g) return fail(GNN_ERR_BAD_ARG, "null group");
+    if (!member_grad && !ensemble_grad && !member_saliency && !ensemble_saliency && !class_rows)
+        return fail(GNN_ERR_BAD_ARG, "every output is null");
+    HIP_TRY(hipSetDevice(g->device));
+    for (gnn_mlp *h : g->m) TRY(check_handle(h)); // (a member's deferred host-batch update is applied first)
+    gnn_mlp *h0 = g->m[0];
+    TRY(check_rows(h0, first, n));
+    const int K = g->K, Lm = h0->L - 1, d0 = h0->dims[0], d_out = h0->dims[Lm], ld0 = h0->ld[0];
+    int block = h0->max_batch;
+    for (gnn_mlp *h : g->m) { TRY(ensure_gx(h)); block = std::min(block, h->max_batch); }
+    hipStream_t st = h0->stream;
+    // [K + 1 maps of d_out x d0 sums][d_out row counts] (one fill) | the members' rows | the ensemble's rows: one readback
+    const size_t cells = (size_t)d_out * d0, rows_f = (size_t)n * d0;
+    const size_t head = sizeof(double) * ((size_t)(K + 1) * cells + (size_t)d_out);
+    const size_t mg_b = member_grad ? sizeof(float) * (size_t)K * rows_f : 0, eg_b = ensemble_grad ? sizeof(float) * rows_f : 0;
+    const bool want_ens = ensemble_grad || ensemble_saliency;
+    DevScratch res, ens;
+    TRY(res.alloc(head + mg_b + eg_b));
+    if (want_ens) TRY(ens.alloc(sizeof(float) * (size_t)pad_up(block) * ld0));
+    HIP_TRY(hipMemsetAsync(res.p, 0, head, st));
+    double *d_sal = res.as<double>();
+    unsigned long long *d_rows = reinterpret_cast<unsigned long long *>(d_sal + (size_t)(K + 1) * cells);
+    float *d_mg = reinterpret_cast<float *>(res.as<char>() + head);
+    float *d_eg = reinterpret_cast<float *>(res.as<char>() + head + mg_b);
+    for (int64_t off = 0; off < n; off += block) {
+        const int B = (int)std::min<int64_t>(block, n - off);
+        const float *y = h0->DY + (size_t)(first + off) * h0->ld[Lm];
+        unsigned long long *count_here = class_rows ? d_rows : nullptr; // the block's rows are counted by ONE of its launches
+        InputGradCombineParams cp{};
+        for (int k = 0; k < K; k++) { // the members one after the other, each through its own handle on the group's stream
+            gnn_mlp *h = g->m[k];
+            const float *a0 = h->DX + (size_t)(first + off) * ld0;
+            do_gradient(h, a0, h->DY + (size_t)(first + off) * h->ld[Lm], B, false, 0.f, 0.f, true);
+            enqueue_input_grad(h, a0, B);
+            if (member_saliency) { enqueue_saliency(h, h->stream, h->gx, y, B, d_sal + (size_t)k * cells, count_here); count_here = nullptr; }
+            if (member_grad) TRY(enqueue_row_copy(h, h->stream, h->gx, B, d_mg + (size_t)k * rows_f + (size_t)off * d0));
+            cp.gx[k] = h->gx;
+        }
+        if (want_ens) {
+            cp.K = K; cp.ens = ens.as<float>(); cp.n4 = (long long)pad_up(B) * ld0 / 4;
+            hipLaunchKernelGGL(input_grad_combine_kernel, dim3((unsigned)((cp.n4 + 255) / 256)), dim3(256), 0, st, cp);
+            if (ensemble_saliency) { enqueue_saliency(h0, st, cp.ens, y, B, d_sal + (size_t)K * cells, count_here); count_here = nullptr; }
+            if (ensemble_grad) TRY(enqueue_row_copy(h0, st, cp.ens, B, d_eg + (size_t)off * d0));
+        }
+        if (count_here) enqueue_saliency(h0, st, h0->gx, y, B, nullptr, count_here);
+    }
+    for (gnn_mlp *h : g->m) TRY_LAUNCHES(h);
+    std::vector<double> host((head + mg_b + eg_b + 7) / 8);
+    HIP_TRY(hipMemcpyAsync(host.data(), res.p, head + mg_b + eg_b, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (member_saliency) std::memcpy(member_saliency, host.data(), sizeof(double) * (size_t)K * cells);
+    if (ensemble_saliency) std::memcpy(ensemble_saliency, host.data() + (size_t)K * cells, sizeof(double) * cells);
+    if (class_rows) {
+        const unsigned long long *c = reinterpret_cast<const unsigned long long *>(host.data() + (size_t)(K + 1) * cells);
+        for (int i = 0; i < d_out; i++) class_rows[i] = (int64_t)c[i];
+    }
+    const char *rows = reinterpret_cast<const char *>(host.data()) + head;
+    if (member_grad) widen(reinterpret_cast<const float *>(rows), member_grad, (size_t)K * rows_f);
+    if (ensemble_grad) widen(reinterpret_cast<const float *>(rows + mg_b), ensemble_grad, rows_f);
+    return GNN_OK;
+}); }
+
+} // extern "C"

@@ -1,0 +1,160 @@
+// input_grad_kernel.h -- which inputs the loss depends on: g = d calculateLoss(x, y) / d x (NN:27, SCE:207-220, GNN:230-242),
+// the l = 0 continuation of the backward loop the reference stops at delta_1 (SCE:272-278), and what consumes it on the device
+// (input_grad.hip: gnn_mlp_input_gradient*, gnn_mlp_group_input_gradient_range).
+//   input_grad_kernel<BF>      gx[b][i] = f'(a0[b][i]) * sum_j delta_1[b][j] * W_0[i][j]: pad(B) rows, ld[0] columns, contraction
+//                              over ld[1].  f' from a0 = f(x) (the reference applies f to the raw input too, SCE:183-186): for the
+//                              leaky pair `a <= 0 ? 0.01 : 1` (MT:235), so an exact-zero pixel gets 0.01.  Both operands are
+//                              k-contiguous in memory -- a row of delta_1, a row of W_0 -- and go from global memory straight to
+//                              registers in MFMA fragment form, 16 B per lane (8 B of bf16), lane group q taking k = 4q..4q+3 of a
+//                              16-deep chunk for BOTH operands (fused_kernels.h: any assignment of k to slots is valid when the
+//                              operands agree).  No LDS, no barrier.  W_0 is the ROW operand (as in the tile kernel): a lane's four
+//                              accumulators are four consecutive columns of one output row, so a0 is one 16-B load and gx one
+//                              16-B store.  One wave per 16 x 16 output tile, the four waves of a workgroup on four neighbouring
+//                              column tiles of the same 16 rows.  BF: the operands are the bf16 shadows (deltab[1], Wb), widened
+//                              to f32 on the way into v_mfma_f32_16x16x4_f32 -- a product of two bf16 values is exact in f32, the
+//                              accumulation is f32 either way, and one kernel body serves both; f' from the unrounded a0.
+//                              Rows >= `rows` and columns >= m_true are written as exact zeros (W_0's pad rows are 0).
+//   saliency_kernel            thread (column i, class c) walks the block's rows in row order and adds (double)|gx[b][i]| of the
+//                              rows whose expected class (confusion_kernel.h: expected_class, MT:186-188) is c into sal[c][i];
+//                              the running sum starts from the value the previous block left, so over a range it is ONE sum in row
+//                              order per cell: no atomics, the same bits every time.  (A thread per cell, not per column: a
+//                              column's d_out sums are independent, and a cell's sum needs one register instead of a map row in
+//                              memory.)  Thread 0 of the first column block also counts the class's rows.
+//   input_grad_combine_kernel  the ensemble's gradient from a table of the members' gx: s = g_0; s += g_k in member order;
+//                              s / (float)K -- the rule of the ensemble's mean output (group_eval_kernel.h).
+#pragma once
+#include "confusion_kernel.h"
+
+namespace gnn {
+
+constexpr int IG_WAVES = 4;  // waves (column tiles) per workgroup
+constexpr int IG_MAXC = 8;   // 16-deep chunks whose loads are in flight at once (IG_MAXC * (4 + 4) VGPRs)
+constexpr int IG_GROUP_MAX = 16; // (= GROUP_MAX of group_kernels.h)
+
+struct InputGradParams {
+    const void *D;   // delta_1 rows, k-contiguous, leading dimension K: float, or __bf16 (BF)
+    const void *W;   // W_0 rows, k-contiguous, leading dimension K: float, or __bf16 (BF)
+    const float *A0; int lda; // a0 = f(x) of the block's rows (read for rows < `rows` only)
+    float *GX; int ldg;       // pad(rows) x M
+    int M, m_true;   // ld[0], d_0
+    int K;           // ld[1]: a multiple of 16
+    int rows;        // live rows of the block
+    int act;
+};
+
+template <bool BF> __device__ __forceinline__ f32x4 ig_load4(const void *base, size_t elem) {
+    if constexpr (BF) {
+        typedef __bf16 ig_bf16x4 __attribute__((ext_vector_type(4)));
+        const ig_bf16x4 v = *reinterpret_cast<const ig_bf16x4 *>(static_cast<const __bf16 *>(base) + elem);
+        return f32x4{(float)v[0], (float)v[1], (float)v[2], (float)v[3]};
+    } else {
+        return *reinterpret_cast<const f32x4 *>(static_cast<const float *>(base) + elem);
+    }
+}
+
+// grid: (ceil(M / 16 / IG_WAVES), pad(rows) / 16)
+template <bool BF>
+static __global__ __launch_bounds__(IG_WAVES * 64) void input_grad_kernel(InputGradParams p) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int fr = lane & 15, fq = lane >> 4;
+    const int i0 = (blockIdx.x * IG_WAVES + wave) * 16, b0 = blockIdx.y * 16;
+    if (i0 >= p.M) return; // (no barrier below)
+    const size_t w_at = (size_t)(i0 + fr) * p.K + 4 * fq, d_at = (size_t)(b0 + fr) * p.K + 4 * fq;
+    const int nc = p.K / 16;
+    f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+    for (int cb = 0; cb < nc; cb += IG_MAXC) {
+        f32x4 w[IG_MAXC], d[IG_MAXC];
+#pragma unroll
+        for (int i = 0; i < IG_MAXC; i++) {
+            if (cb + i < nc) {
+                w[i] = ig_load4<BF>(p.W, w_at + (size_t)(cb + i) * 16);
+                d[i] = ig_load4<BF>(p.D, d_at + (size_t)(cb + i) * 16);
+            } else {
+                w[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+                d[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < IG_MAXC; i++) {
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                if (i & 1) acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w[i][j], d[i][j], acc1, 0, 0, 0);
+                else acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w[i][j], d[i][j], acc0, 0, 0, 0);
+            }
+        }
+    }
+    const f32x4 acc = acc0 + acc1;
+    // C / D layout: column (here: batch row) = lane & 15, rows (here: input columns) = 4 * (lane >> 4) + r
+    const int b = b0 + fr, col = i0 + 4 * fq;
+    f32x4 o = {0.f, 0.f, 0.f, 0.f};
+    if (b < p.rows) {
+        const f32x4 a = *reinterpret_cast<const f32x4 *>(p.A0 + (size_t)b * p.lda + col);
+#pragma unroll
+        for (int r = 0; r < 4; r++) o[r] = col + r < p.m_true ? acc[r] * act_prime_from_a(p.act, a[r]) : 0.f;
+    }
+    *reinterpret_cast<f32x4 *>(p.GX + (size_t)b * p.ldg + col) = o;
+}
+
+constexpr int SAL_NT = 256;
+constexpr int SAL_FLIGHT = 32; // rows a thread has loaded ahead of its sum (a divisor of SAL_NT)
+struct SaliencyParams {
+    const float *GX; int ldg; // the block's gradient rows
+    int d0, rows, n_out;
+    const float *Y; int ldy;  // expected rows of the block
+    double *sal;                    // [n_out][d0], may be null
+    unsigned long long *class_rows; // [n_out], may be null
+};
+
+// grid: (ceil(d0 / SAL_NT), n_out)
+static __global__ __launch_bounds__(SAL_NT) void saliency_kernel(SaliencyParams p) {
+    __shared__ int cls[SAL_NT];
+    const int t = threadIdx.x, i = blockIdx.x * SAL_NT + t, c = blockIdx.y;
+    const bool own = p.sal && i < p.d0;
+    const bool counts = p.class_rows && blockIdx.x == 0 && t == 0;
+    double acc = own ? p.sal[(size_t)c * p.d0 + i] : 0.0;
+    unsigned long long cnt = 0;
+    const float *gx = p.GX + (own ? i : 0);
+    for (int r0 = 0; r0 < p.rows; r0 += SAL_NT) {
+        __syncthreads();
+        cls[t] = r0 + t < p.rows ? expected_class(p.Y + (size_t)(r0 + t) * p.ldy, p.n_out) : -1;
+        __syncthreads();
+        const int m = p.rows - r0 < SAL_NT ? p.rows - r0 : SAL_NT;
+        if (own) {
+            // every row is loaded and the other classes' rows add 0.0 (exact: acc >= 0), so the loads do not wait for the sum:
+            // SAL_FLIGHT of them are in flight at once (the walk is bound by their latency, one L2 round trip per batch)
+            // (rows past the block's end: the last row again, loaded without a branch and added as 0.0 -- their class is -1)
+            for (int j0 = 0; j0 < m; j0 += SAL_FLIGHT) {
+                float v[SAL_FLIGHT];
+#pragma unroll
+                for (int u = 0; u < SAL_FLIGHT; u++) v[u] = gx[(size_t)(r0 + (j0 + u < m ? j0 + u : m - 1)) * p.ldg];
+#pragma unroll
+                for (int u = 0; u < SAL_FLIGHT; u++) acc += cls[j0 + u] == c ? (double)fabsf(v[u]) : 0.0;
+            }
+        }
+        if (counts) for (int j = 0; j < m; j++) cnt += cls[j] == c ? 1ull : 0ull;
+    }
+    if (own) p.sal[(size_t)c * p.d0 + i] = acc;
+    if (counts) p.class_rows[c] += cnt;
+}
+
+struct InputGradCombineParams {
+    const float *gx[IG_GROUP_MAX]; // member k's gradient rows of the block
+    int K;
+    float *ens;
+    long long n4;                  // float4 elements: pad(rows) * ld[0] / 4
+};
+static __global__ __launch_bounds__(256) void input_grad_combine_kernel(InputGradCombineParams p) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= p.n4) return;
+    const float kf = (float)p.K;
+    f32x4 s = reinterpret_cast<const f32x4 *>(p.gx[0])[i];
+#pragma unroll
+    for (int k = 1; k < IG_GROUP_MAX; k++) // (unrolled: the table is read with constant offsets into the arguments)
+        if (k < p.K) s += reinterpret_cast<const f32x4 *>(p.gx[k])[i];
+    f32x4 o;
+#pragma unroll
+    for (int r = 0; r < 4; r++) o[r] = s[r] / kf;
+    reinterpret_cast<f32x4 *>(p.ens)[i] = o;
+}
+
+} // namespace gnn

@@ -268,6 +268,37 @@ class NeuralNet:
         _capi.check(self._lib.gnn_mlp_evaluate_range(self._h, first, n, None, None, None, lab.ctypes.data_as(C.POINTER(C.c_int32))))
         return lab
 
+    # -- which inputs the loss depends on: csrc/input_grad_kernel.h ----------------------------------
+    def input_gradient(self, X, Y):
+        """d calculateLoss(x, y) / d x (NN:27; SCE:272-278 continued to the input), one row per input row; a 1-D input gets a
+        1-D result, as propagate does.  Leaves the gradient buffer holding this batch's weight gradient; changes no weight."""
+        single = np.ndim(X) == 1
+        X = _f64(X, self.layer_dims[0])
+        Y = _f64(Y, self.layer_dims[-1])
+        if X.shape[0] != Y.shape[0]:
+            raise ValueError("input / expected row counts differ")
+        g = np.empty(X.shape)
+        _capi.check(self._lib.gnn_mlp_input_gradient(self._h, _dp(X), _dp(Y), X.shape[0], _dp(g)))
+        return g[0] if single else g
+
+    def input_gradient_range(self, first=0, n=None, grad=True, saliency=False):
+        """The same over dataset rows [first, first + n), any n, in one call: the gradients (n, d_0); with saliency=True
+        (saliency (d_out, d_0), class_rows (d_out,)) as well -- saliency[e] is the sum of |gradient| over the rows whose
+        expected class (MT:186-188) is e, class_rows[e] their number.  grad=False, saliency=True returns the pair alone."""
+        first, n = self._rows(first, n)
+        if not grad and not saliency:
+            raise ValueError("nothing asked for")
+        d0, d = self.layer_dims[0], self.layer_dims[-1]
+        g = np.empty((max(n, 0), d0)) if grad else None
+        sal = np.zeros((d, d0)) if saliency else None
+        rows = np.zeros(d, dtype=np.int64) if saliency else None
+        _capi.check(self._lib.gnn_mlp_input_gradient_range(
+            self._h, first, n, _dp(g) if grad else None, _dp(sal) if saliency else None,
+            rows.ctypes.data_as(C.POINTER(C.c_int64)) if saliency else None))
+        if not saliency:
+            return g
+        return (g, sal, rows) if grad else (sal, rows)
+
     # -- data-parallel hooks ------------------------------------------------------------------
     @property
     def grad_elems(self):
@@ -630,6 +661,24 @@ class NetGroup:
             self._h, first, n, member.ctypes.data_as(i64), ens.ctypes.data_as(i64),
             lab.ctypes.data_as(C.POINTER(C.c_int32)) if labels else None))
         return (member, ens, lab) if labels else (member, ens)
+
+    def input_gradient_range(self, first=0, n=None, members=False, saliency=False):
+        """The ensemble's input gradient over the rows, (n, d_0): the mean of the members' gradients (f32, member order, one
+        division by K, as ensemble_propagate_range forms the mean output).  members=True: (member (K, n, d_0), ensemble).
+        saliency=True appends (ensemble_saliency (d_out, d_0), class_rows (d_out,)), and with members=True the members' maps
+        (K, d_out, d_0) in front of them: (member, ensemble, member_saliency, ensemble_saliency, class_rows)."""
+        first, n = self._rows(first, n)
+        k, d0, d = len(self), self.layer_dims[0], self.layer_dims[-1]
+        ens = np.empty((max(n, 0), d0))
+        mem = np.empty((k, max(n, 0), d0)) if members else None
+        msal = np.zeros((k, d, d0)) if members and saliency else None
+        esal = np.zeros((d, d0)) if saliency else None
+        rows = np.zeros(d, dtype=np.int64) if saliency else None
+        _capi.check(self._lib.gnn_mlp_group_input_gradient_range(
+            self._h, first, n, _dp(mem) if mem is not None else None, _dp(ens), _dp(msal) if msal is not None else None,
+            _dp(esal) if saliency else None, rows.ctypes.data_as(C.POINTER(C.c_int64)) if saliency else None))
+        out = ((mem, ens) if members else (ens,)) + (((msal,) if members else ()) + (esal, rows) if saliency else ())
+        return out[0] if len(out) == 1 else out
 
 
 class DataParallelNeuralNet:

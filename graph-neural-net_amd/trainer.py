@@ -224,6 +224,14 @@ def per_class(conf):
     return recall, precision
 
 
+def fgsm(net, X, Y, eps, clip=(0.0, 1.0)):
+    """The fast-gradient-sign perturbation of the rows: clip(X + eps * sign(g)), g = net.input_gradient(X, Y).  Computed on the
+    host: the device holds f(x), not x.  clip=None leaves the rows unclipped."""
+    X = np.asarray(X, dtype=np.float64)
+    out = X + float(eps) * np.sign(net.input_gradient(X, Y))
+    return out if clip is None else np.clip(out, clip[0], clip[1])
+
+
 def train_log_row(net_dim, iterations, step_size, batch_size, momentum, noise, training_acc, test_acc):
     """The row MNISTTrainer.logTest appends to logs/trainLog.csv (MT:211-219):
     `dims,iterations,step,batch,momentum,noise,trainAcc,testAcc` in the reference's number formats

@@ -176,6 +176,22 @@ int gnn_mlp_count_hits_range(gnn_mlp_t *h, int64_t first, int64_t n, int64_t *hi
 int gnn_mlp_evaluate_range(gnn_mlp_t *h, int64_t first, int64_t n, int64_t *hits, double *loss_sum,
                            int64_t *confusion /* [d_out][d_out] */, int32_t *labels /* [n] */);
 
+/* Which inputs the loss depends on: grad[b * d_0 + i] = d calculateLoss(X_b, Y_b) / d X_b[i] (NN:27, SCE:207-220, GNN:230-242)
+ * -- the l = 0 continuation of the backward loop the reference stops at delta_1 (SCE:272-278):
+ * (delta_1 . W_0^T) * f'(x), f' because the reference applies f to the raw input too (SCE:183-186); f' is taken from f(x), for
+ * the leaky pair `<= 0 ? 0.01 : 1` (MT:235), so an exact-zero input gets 0.01.  With two layers delta_1 is the output delta.
+ * bf16 handles take delta_1 and W_0 rounded to bf16 with f32 accumulation.  Host rows, 1 <= B <= max_batch.  The handle's
+ * own gradient computation runs first: like gnn_mlp_compute_gradient* the call leaves the gradient buffer holding (its last
+ * block's) weight gradient; it changes no weight, momentum, step count or sampler, and a deferred host-batch update is applied
+ * first.  Works on borrowed handles and on every plan (csrc/input_grad_kernel.h: one more launch per block of rows). */
+int gnn_mlp_input_gradient(gnn_mlp_t *h, const double *X, const double *Y, int B, double *grad /* [B][d_0] */);
+/* The same over the dataset rows [first, first + n), any n, in blocks of max_batch with no host work in between and ONE
+ * readback: grad as above; saliency[e * d_0 + i] = the sum of |grad[.][i]| over the rows whose expected class (MT:186-188) is e,
+ * added in fp64 in row order (the same bits every time); class_rows[e] = the number of those rows.  Each of the three may be
+ * null, not all of them. */
+int gnn_mlp_input_gradient_range(gnn_mlp_t *h, int64_t first, int64_t n, double *grad /* [n][d_0] or null */,
+                                 double *saliency /* [d_out][d_0] or null */, int64_t *class_rows /* [d_out] or null */);
+
 /* ---- the trainer's sampling loop (NeuralNetTrainer.java) ------------------------------------ */
 
 /* Epoch sampler without replacement, NNT:28-43 + NNT:143-168: java.util.Random(seed) (the
@@ -393,6 +409,17 @@ int gnn_mlp_group_ensemble_range(gnn_mlp_group_t *g, int64_t first, int64_t n, d
  * momentum, step count or look-ahead state; each member's deferred host-batch update is applied first. */
 int gnn_mlp_group_confusion_range(gnn_mlp_group_t *g, int64_t first, int64_t n, int64_t *member_confusion /* [K][d_out][d_out] */,
                                   int64_t *ensemble_confusion /* [d_out][d_out] */, int32_t *member_labels /* [K][n] */);
+/* gnn_mlp_input_gradient_range (NN:27, SCE:207-220, GNN:230-242; SCE:272-278 continued to the input) for every member and for
+ * the ensemble: the members run one after the other through their borrowed handles on the group's stream, block by block; the
+ * ensemble's gradient is the members' mean formed as gnn_mlp_group_ensemble_range forms the mean output -- f32, member order,
+ * one division by (float)K -- and its saliency is summed from that.  member_grad[(k * n + r) * d_0 + i], member_saliency
+ * [(k * d_out + e) * d_0 + i]; each of the five may be null, not all of them.  One readback.  Every member's gradient buffer
+ * holds its last block's weight gradient afterwards; no weight, momentum, step count or sampler changes. */
+int gnn_mlp_group_input_gradient_range(gnn_mlp_group_t *g, int64_t first, int64_t n, double *member_grad /* [K][n][d_0] or null */,
+                                       double *ensemble_grad /* [n][d_0] or null */,
+                                       double *member_saliency /* [K][d_out][d_0] or null */,
+                                       double *ensemble_saliency /* [d_out][d_0] or null */,
+                                       int64_t *class_rows /* [d_out] or null */);
 
 /* ---- shape specialisation ---------------------------------------------------------------------
  * The per-row-block kernel of the fused small-net path is a template over the net's shape; with
