@@ -101,6 +101,20 @@ SYMBOLS = [
     ("gnn_mlp_group_ensemble_range", C.c_int, [_H, C.c_int64, C.c_int64, _dp, _ip]),
     ("gnn_mlp_group_confusion_range", C.c_int, [_H, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _ip]),
     ("gnn_mlp_group_input_gradient_range", C.c_int, [_H, C.c_int64, C.c_int64, _dp, _dp, _dp, _dp, C.POINTER(C.c_int64)]),
+    ("gnn_mlp_upload_held_out", C.c_int, [_H, _dp, _dp, C.c_int64]),
+    ("gnn_mlp_upload_held_out_u8", C.c_int, [_H, _u8, _u8, C.c_int64]),
+    ("gnn_mlp_set_rows", C.c_int64, [_H, C.c_int]),
+    ("gnn_mlp_evaluate_set_range", C.c_int, [_H, C.c_int, C.c_int64, C.c_int64, C.POINTER(C.c_int64), _dp, C.POINTER(C.c_int64), _ip]),
+    ("gnn_mlp_held_out_points", C.c_int, [C.c_int, C.c_int]),
+    ("gnn_mlp_train_sampled_held_out", C.c_int, [_H, _H, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int64, C.c_int,
+                                                 C.POINTER(C.c_int64), _dp, _ip, _dp]),
+    ("gnn_mlp_group_upload_held_out", C.c_int, [_H, _dp, _dp, C.c_int64]),
+    ("gnn_mlp_group_upload_held_out_u8", C.c_int, [_H, _u8, _u8, C.c_int64]),
+    ("gnn_mlp_group_evaluate_set_range", C.c_int, [_H, C.c_int, C.c_int64, C.c_int64, C.POINTER(C.c_int64), _dp, C.POINTER(C.c_int64)]),
+    ("gnn_mlp_group_ensemble_set_range", C.c_int, [_H, C.c_int, C.c_int64, C.c_int64, _dp, _ip]),
+    ("gnn_mlp_group_confusion_set_range", C.c_int, [_H, C.c_int, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _ip]),
+    ("gnn_mlp_group_train_sampled_held_out", C.c_int, [_H, C.POINTER(_H), C.c_int, _ip, _dp, _dp, C.c_int, C.c_int, C.c_int64, C.c_int,
+                                                       C.POINTER(C.c_int64), _dp, C.POINTER(C.c_int64), _ip, _dp]),
     ("gnn_mlp_forget_lookahead", C.c_int, [_H]),
     ("gnn_mlp_advance_time", C.c_int, [_H, C.c_int]),
     ("gnn_mlp_recover_stream", C.c_int, [_H]),

@@ -284,6 +284,8 @@ void destroy_handle(gnn_mlp *h) {
     fr(h->logits); fr(h->prob); fr(h->ybuf); fr(h->lossv); fr(h->labels); fr(h->idxbuf);
     fr(h->stage_out); release_host_staging(h); fr(h->slabs); fr(h->ts_map); fr(h->ts_map0);
     if (!h->shared_dataset) { fr(h->DX); fr(h->DY); fr(h->DXb); }
+    if (!h->shared_held) { fr(h->held.X); fr(h->held.Y); fr(h->held.Xb); }
+    fr(h->best_W); fr(h->best_hist);
     fr(h->Wb);
     for (int i = 0; i < 2; i++) { fr(h->xstage[i]); fr(h->xstage_b[i]); }
     for (__bf16 *p : h->actb) fr(p);
@@ -408,17 +410,24 @@ int gnn_mlp_get_momentum(gnn_mlp_t *h, double *flat) { return guarded([&]() -> i
 int gnn_mlp_set_momentum(gnn_mlp_t *h, const double *flat) { return guarded([&]() -> int { TRY(check_handle(h)); return set_flat(h, h->V, flat); }); }
 
 // ---- dataset ------------------------------------------------------------------------------
-static int alloc_dataset(gnn_mlp *h, int64_t N) { return guarded([&]() -> int {
+// (the set's buffers through references: the training set's are the handle's DX / DY / DXb, which every training path reads)
+struct SetSlots { float *&X, *&Y; __bf16 *&Xb; int64_t &n; };
+static SetSlots set_slots(gnn_mlp *h, int set) {
+    if (set == GNN_SET_HELD_OUT) return SetSlots{h->held.X, h->held.Y, h->held.Xb, h->held.n};
+    return SetSlots{h->DX, h->DY, h->DXb, h->dataset_n};
+}
+static int alloc_dataset(gnn_mlp *h, int64_t N, int set) { return guarded([&]() -> int {
     HIP_TRY(hipStreamSynchronize(h->stream)); // nothing in flight may still read the old dataset
-    if (h->DX) { (void)hipFree(h->DX); h->DX = nullptr; }
-    if (h->DY) { (void)hipFree(h->DY); h->DY = nullptr; }
-    if (h->DXb) { (void)hipFree(h->DXb); h->DXb = nullptr; }
-    h->dataset_n = 0;
-    h->la.rows_renamed(); // (they name rows of the old dataset)
+    const SetSlots d = set_slots(h, set);
+    if (d.X) { (void)hipFree(d.X); d.X = nullptr; }
+    if (d.Y) { (void)hipFree(d.Y); d.Y = nullptr; }
+    if (d.Xb) { (void)hipFree(d.Xb); d.Xb = nullptr; }
+    d.n = 0;
+    if (set == GNN_SET_TRAIN) h->la.rows_renamed(); // (they name rows of the old dataset; the held-out set is never named)
     const size_t rows = (size_t)N + PAD; // PAD zero rows behind the last sample: a batch's padding rows read them
-    TRY(dev_alloc(&h->DX, rows * h->ld[0], h->stream));
-    TRY(dev_alloc(&h->DY, rows * h->ld[h->L - 1], h->stream));
-    if (h->dtype == GNN_DTYPE_BF16) TRY(dev_alloc(&h->DXb, rows * h->ld[0], h->stream));
+    TRY(dev_alloc(&d.X, rows * h->ld[0], h->stream));
+    TRY(dev_alloc(&d.Y, rows * h->ld[h->L - 1], h->stream));
+    if (h->dtype == GNN_DTYPE_BF16) TRY(dev_alloc(&d.Xb, rows * h->ld[0], h->stream));
     return GNN_OK;
 }); }
 
@@ -433,11 +442,27 @@ int gnn_mlp_upload_dataset_u8(gnn_mlp_t *h, const uint8_t *pixels, const uint8_t
     if (h->group) return fail(GNN_ERR_STATE, kMemberData);
     return upload_dataset_u8(h, pixels, labels, N);
 }); }
+static const char *kMemberHeld = "a member of a group sees the group's held-out set (gnn_mlp_group_upload_held_out)";
+int gnn_mlp_upload_held_out(gnn_mlp_t *h, const double *X, const double *Y, int64_t N) { return guarded([&]() -> int {
+    TRY(check_handle(h, false)); // (a pending host-batch update stays pending: the upload reads and writes nothing of it)
+    if (h->group) return fail(GNN_ERR_STATE, kMemberHeld);
+    return upload_dataset_f64(h, X, Y, N, GNN_SET_HELD_OUT);
+}); }
+int gnn_mlp_upload_held_out_u8(gnn_mlp_t *h, const uint8_t *pixels, const uint8_t *labels, int64_t N) { return guarded([&]() -> int {
+    TRY(check_handle(h, false)); // (a pending host-batch update stays pending: the upload reads and writes nothing of it)
+    if (h->group) return fail(GNN_ERR_STATE, kMemberHeld);
+    return upload_dataset_u8(h, pixels, labels, N, GNN_SET_HELD_OUT);
+}); }
+int64_t gnn_mlp_set_rows(const gnn_mlp_t *h, int set) {
+    if (!h || (set != GNN_SET_TRAIN && set != GNN_SET_HELD_OUT)) return -1;
+    return resident_set(h, set).n;
+}
 } // extern "C"
 
-int gnn::host::upload_dataset_f64(gnn_mlp *h, const double *X, const double *Y, int64_t N) {
+int gnn::host::upload_dataset_f64(gnn_mlp *h, const double *X, const double *Y, int64_t N, int set) {
     if (!X || !Y || N <= 0) return fail(GNN_ERR_BAD_ARG, "bad dataset");
-    TRY(alloc_dataset(h, N));
+    TRY(alloc_dataset(h, N, set));
+    const SetSlots d = set_slots(h, set);
     const int d0 = h->dims[0], dl = h->dims[h->L - 1];
     const int64_t chunk = 4096;
     DevScratch bx, by;
@@ -451,20 +476,21 @@ int gnn::host::upload_dataset_f64(gnn_mlp *h, const double *X, const double *Y, 
         if (err == hipSuccess)
             err = hipMemcpyAsync(sy, Y + r0 * dl, sizeof(double) * n * dl, hipMemcpyHostToDevice, h->stream);
         if (err != hipSuccess) break;
-        launch_convert_rows(h, sx, d0, h->DX + (size_t)r0 * h->ld[0], h->ld[0], n, n, h->inner_act, 1);
-        launch_convert_rows(h, sy, dl, h->DY + (size_t)r0 * h->ld[h->L - 1], h->ld[h->L - 1], n, n, 0, 0);
+        launch_convert_rows(h, sx, d0, d.X + (size_t)r0 * h->ld[0], h->ld[0], n, n, h->inner_act, 1);
+        launch_convert_rows(h, sy, dl, d.Y + (size_t)r0 * h->ld[h->L - 1], h->ld[h->L - 1], n, n, 0, 0);
         err = hipStreamSynchronize(h->stream); // the staging buffers are reused by the next chunk
     }
     if (err != hipSuccess) return fail(GNN_ERR_HIP, std::string("dataset upload: ") + hipGetErrorString(err));
-    if (h->DXb) { to_bf16(h, h->DX, h->DXb, ((size_t)N + PAD) * h->ld[0]); HIP_TRY(hipStreamSynchronize(h->stream)); }
+    if (d.Xb) { to_bf16(h, d.X, d.Xb, ((size_t)N + PAD) * h->ld[0]); HIP_TRY(hipStreamSynchronize(h->stream)); }
     TRY_LAUNCHES(h);
-    h->dataset_n = N;
+    d.n = N;
     return GNN_OK;
 }
 
-int gnn::host::upload_dataset_u8(gnn_mlp *h, const uint8_t *pixels, const uint8_t *labels, int64_t N) {
+int gnn::host::upload_dataset_u8(gnn_mlp *h, const uint8_t *pixels, const uint8_t *labels, int64_t N, int set) {
     if (!pixels || !labels || N <= 0) return fail(GNN_ERR_BAD_ARG, "bad dataset");
-    TRY(alloc_dataset(h, N));
+    TRY(alloc_dataset(h, N, set));
+    const SetSlots d = set_slots(h, set);
     const int d0 = h->dims[0], dl = h->dims[h->L - 1];
     DevScratch bp, bl;
     TRY(bp.alloc((size_t)N * d0));
@@ -472,12 +498,12 @@ int gnn::host::upload_dataset_u8(gnn_mlp *h, const uint8_t *pixels, const uint8_
     uint8_t *sp = bp.as<uint8_t>(), *sl = bl.as<uint8_t>();
     HIP_TRY(hipMemcpyAsync(sp, pixels, (size_t)N * d0, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(sl, labels, (size_t)N, hipMemcpyHostToDevice, h->stream));
-    launch_encode_u8(h, sp, d0, h->DX, h->ld[0], N, h->inner_act);
-    launch_onehot_u8(h, sl, dl, h->DY, h->ld[h->L - 1], N);
+    launch_encode_u8(h, sp, d0, d.X, h->ld[0], N, h->inner_act);
+    launch_onehot_u8(h, sl, dl, d.Y, h->ld[h->L - 1], N);
     HIP_TRY(hipStreamSynchronize(h->stream)); // the scratch buffers are released when this function returns
-    if (h->DXb) { to_bf16(h, h->DX, h->DXb, ((size_t)N + PAD) * h->ld[0]); HIP_TRY(hipStreamSynchronize(h->stream)); }
+    if (d.Xb) { to_bf16(h, d.X, d.Xb, ((size_t)N + PAD) * h->ld[0]); HIP_TRY(hipStreamSynchronize(h->stream)); }
     TRY_LAUNCHES(h);
-    h->dataset_n = N;
+    d.n = N;
     return GNN_OK;
 }
 
@@ -655,11 +681,17 @@ int gnn_mlp_count_hits_range(gnn_mlp_t *h, int64_t first, int64_t n, int64_t *hi
 // (validate() of NNT:102-113 without its division; sum_loss_kernel block after block into ONE slot: one fixed order, the same
 // bits every time) and the confusion matrix of the labels (confusion_kernel.h, one table), the labels themselves on request.
 int gnn_mlp_evaluate_range(gnn_mlp_t *h, int64_t first, int64_t n, int64_t *hits, double *loss_sum, int64_t *confusion,
-                           int32_t *labels) { return guarded([&]() -> int {
+                           int32_t *labels) {
+    return gnn_mlp_evaluate_set_range(h, GNN_SET_TRAIN, first, n, hits, loss_sum, confusion, labels);
+}
+
+// ... on either resident set (handle.h: resident_set): testOnTrainingData / testOnTestData, MT:159-197
+int gnn_mlp_evaluate_set_range(gnn_mlp_t *h, int set, int64_t first, int64_t n, int64_t *hits, double *loss_sum, int64_t *confusion,
+                               int32_t *labels) { return guarded([&]() -> int {
     TRY(check_handle(h));
     if (!hits && !loss_sum && !confusion && !labels) return fail(GNN_ERR_BAD_ARG, "every output is null");
-    if (!h->DX) return fail(GNN_ERR_STATE, "no dataset uploaded");
-    if (n <= 0 || first < 0 || first + n > h->dataset_n) return fail(GNN_ERR_BAD_ARG, "rows outside the dataset");
+    TRY(check_set_rows(h, set, first, n));
+    const ResidentSet rs = resident_set(h, set);
     const int Lm = h->L - 1, d_out = h->dims[Lm];
     // [hit counter][loss sum][d_out x d_out counters][n labels]: one fill, one readback
     const size_t cells = (size_t)d_out * d_out;
@@ -670,24 +702,7 @@ int gnn_mlp_evaluate_range(gnn_mlp_t *h, int64_t first, int64_t n, int64_t *hits
     unsigned long long *d_hits = res.as<unsigned long long>();
     static_assert(sizeof(unsigned long long) == sizeof(double), "one buffer for counters and the sum");
     double *d_loss = reinterpret_cast<double *>(d_hits + 1);
-    const int block = eval_block_rows(h, n);
-    int rc_ws = GNN_OK;
-    EvalScope scope(h, block, &rc_ws);
-    if (rc_ws != GNN_OK) return rc_ws;
-    for (int64_t off = 0; off < n; off += block) {
-        const int B = (int)std::min<int64_t>(block, n - off);
-        const float *y = h->DY + (size_t)(first + off) * h->ld[Lm];
-        do_forward(h, h->DX + (size_t)(first + off) * h->ld[0], y, B, false, true, true);
-        hipLaunchKernelGGL(count_hits_kernel, dim3((B + 255) / 256), dim3(256), 0, h->stream,
-                           HitsParams{h->labels, y, h->ld[Lm], d_out, B, d_hits});
-        hipLaunchKernelGGL(sum_loss_kernel, dim3(1), dim3(256), 0, h->stream, LossSumParams{h->lossv, B, d_loss, off > 0 ? 1 : 0});
-        ConfusionParams cf{};
-        cf.label[0] = h->labels; cf.T = 1; cf.rows = B; cf.n_out = d_out; cf.Y = y; cf.ldy = h->ld[Lm];
-        cf.counts = d_hits + 2;
-        cf.labels_out = labels ? reinterpret_cast<int32_t *>(res.as<char>() + head) : nullptr;
-        cf.T_copy = 1; cf.out_stride = n; cf.row_offset = off;
-        HIP_TRY(launch_confusion(cf, h->stream));
-    }
+    TRY(enqueue_evaluation(h, rs, first, n, d_hits, d_loss, d_hits + 2, labels ? reinterpret_cast<int32_t *>(res.as<char>() + head) : nullptr));
     TRY_LAUNCHES(h);
     std::vector<unsigned long long> host((head + lab_b + 7) / 8);
     HIP_TRY(hipMemcpyAsync(host.data(), res.p, head + lab_b, hipMemcpyDeviceToHost, h->stream));
@@ -698,6 +713,45 @@ int gnn_mlp_evaluate_range(gnn_mlp_t *h, int64_t first, int64_t n, int64_t *hits
     if (labels) std::memcpy(labels, reinterpret_cast<const char *>(host.data()) + head, lab_b);
     return GNN_OK;
 }); }
+
+} // extern "C"
+
+int gnn::host::check_set_rows(const gnn_mlp *h, int set, int64_t first, int64_t n) {
+    if (set != GNN_SET_TRAIN && set != GNN_SET_HELD_OUT) return fail(GNN_ERR_BAD_ARG, "set: GNN_SET_TRAIN or GNN_SET_HELD_OUT");
+    const ResidentSet rs = resident_set(h, set);
+    if (!rs.X) return fail(GNN_ERR_STATE, set == GNN_SET_TRAIN ? "no dataset uploaded" : "no held-out set uploaded");
+    if (n <= 0 || first < 0 || first + n > rs.n) return fail(GNN_ERR_BAD_ARG, set == GNN_SET_TRAIN ? "rows outside the dataset" : "rows outside the held-out set");
+    return GNN_OK;
+}
+
+// One block of rows after the other on the stream: forward + output rule + `>=` argmax, the hits, the block's loss sum into the
+// ONE slot, and (cf_counts) the confusion launch.  Nothing is waited for; the evaluation workspace is grown first if it must be.
+int gnn::host::enqueue_evaluation(gnn_mlp *h, const ResidentSet &rs, int64_t first, int64_t n, unsigned long long *d_hits, double *d_loss,
+                                  unsigned long long *cf_counts, int32_t *labels_out) {
+    const int Lm = h->L - 1, d_out = h->dims[Lm];
+    const int block = eval_block_rows(h, n);
+    int rc_ws = GNN_OK;
+    EvalScope scope(h, block, &rc_ws);
+    if (rc_ws != GNN_OK) return rc_ws;
+    for (int64_t off = 0; off < n; off += block) {
+        const int B = (int)std::min<int64_t>(block, n - off);
+        const float *y = rs.Y + (size_t)(first + off) * h->ld[Lm];
+        do_forward(h, rs.X + (size_t)(first + off) * h->ld[0], y, B, false, true, true);
+        hipLaunchKernelGGL(count_hits_kernel, dim3((B + 255) / 256), dim3(256), 0, h->stream,
+                           HitsParams{h->labels, y, h->ld[Lm], d_out, B, d_hits});
+        hipLaunchKernelGGL(sum_loss_kernel, dim3(1), dim3(256), 0, h->stream, LossSumParams{h->lossv, B, d_loss, off > 0 ? 1 : 0});
+        if (!cf_counts) continue;
+        ConfusionParams cf{};
+        cf.label[0] = h->labels; cf.T = 1; cf.rows = B; cf.n_out = d_out; cf.Y = y; cf.ldy = h->ld[Lm];
+        cf.counts = cf_counts;
+        cf.labels_out = labels_out;
+        cf.T_copy = 1; cf.out_stride = n; cf.row_offset = off;
+        HIP_TRY(launch_confusion(cf, h->stream));
+    }
+    return GNN_OK;
+}
+
+extern "C" {
 
 // ---- data-parallel hooks --------------------------------------------------------------------
 int gnn_mlp_grad_device_ptr(gnn_mlp_t *h, void **dev_ptr) { return guarded([&]() -> int {

@@ -194,6 +194,28 @@ int gnn_mlp_group_upload_dataset_u8(gnn_mlp_group_t *g, const uint8_t *pixels, c
     return share_dataset(g);
 }); }
 
+// the held-out set: member 0's too, borrowed by the others -- no look-ahead state names its rows
+static int share_held(gnn_mlp_group *g) {
+    for (int k = 1; k < g->K; k++) { g->m[k]->held = g->m[0]->held; g->m[k]->shared_held = true; }
+    return GNN_OK;
+}
+
+int gnn_mlp_group_upload_held_out(gnn_mlp_group_t *g, const double *X, const double *Y, int64_t N) { return guarded([&]() -> int {
+    TRY(check_group(g));
+    for (gnn_mlp *h : g->m) TRY(check_handle(h, false));
+    const int rc = upload_dataset_f64(g->m[0], X, Y, N, GNN_SET_HELD_OUT);
+    share_held(g); // (after a failed upload too: the old set is gone for every member)
+    return rc;
+}); }
+
+int gnn_mlp_group_upload_held_out_u8(gnn_mlp_group_t *g, const uint8_t *pixels, const uint8_t *labels, int64_t N) { return guarded([&]() -> int {
+    TRY(check_group(g));
+    for (gnn_mlp *h : g->m) TRY(check_handle(h, false));
+    const int rc = upload_dataset_u8(g->m[0], pixels, labels, N, GNN_SET_HELD_OUT);
+    share_held(g);
+    return rc;
+}); }
+
 int gnn_mlp_group_train_range(gnn_mlp_group_t *g, int64_t first, int B, int n_steps, const double *steps,
                               const double *momenta) { return guarded([&]() -> int {
     TRY(check_group(g));
@@ -541,6 +563,138 @@ int gnn_mlp_group_train_sampled_sizes(gnn_mlp_group_t *g, gnn_sampler_t *const *
         HIP_TRY(hipMemcpy(col.data(), val.p, sizeof(double) * col.size(), hipMemcpyDeviceToHost));
         for (int k = 0; k < K; k++)
             for (int i = 0; i < iterations; i++) val_loss[(size_t)i * K + k] = col[(size_t)k * iterations + i] / (double)validation_size; // NNT:112
+    }
+    return GNN_OK;
+}); }
+
+} // extern "C"
+
+/* The held-out curve of a group (include/gnn_mlp.h: gnn_mlp_group_train_sampled_held_out): the sized loop above with, behind the
+ * iterations that end an interval and still under the GroupScope, the launches of gnn_mlp_group_evaluate_set_range over the
+ * held-out rows -- their results left in slot p of a device buffer [P][K hit counters, the ensemble's, K loss sums] -- and ONE
+ * keep_best launch for all members (keep_best_kernel.h).  Groups without grouped launches train interval by interval, member
+ * after member through their own handles (a lone loop cut into calls ends on the same bits), the point behind every interval. */
+namespace {
+struct GroupHeldOut : SampledObserver {
+    gnn_mlp_group *g; int iterations, every, rule, P; int64_t held_rows;
+    unsigned long long *d_res; double *d_slots;
+    bool want_weights;
+    std::vector<unsigned long long> res; std::vector<KeepBestRecord> best; std::vector<float> w;
+    size_t words() const { return 2 * (size_t)g->K + 1; }
+    int point(int p) {
+        unsigned long long *hits = d_res + (size_t)p * words();
+        double *sums = reinterpret_cast<double *>(hits + (g->K + 1));
+        TRY(enqueue_group_point(g, held_rows, hits, sums, d_slots));
+        return launch_keep_best(g->m[0]->stream, g->m.data(), g->K, hits, sums, p, rule);
+    }
+    int readbacks() {
+        hipStream_t st = g->m[0]->stream;
+        HIP_TRY(hipMemcpyAsync(res.data(), d_res, sizeof(unsigned long long) * res.size(), hipMemcpyDeviceToHost, st));
+        for (int k = 0; k < g->K; k++) {
+            const gnn_mlp *h = g->m[(size_t)k];
+            HIP_TRY(hipMemcpyAsync(&best[(size_t)k], h->best_hist + (P - 1), sizeof(KeepBestRecord), hipMemcpyDeviceToHost, st));
+            if (want_weights) HIP_TRY(hipMemcpyAsync(w.data() + (size_t)k * h->n_pad, h->best_W, sizeof(float) * (size_t)h->n_pad, hipMemcpyDeviceToHost, st));
+        }
+        return GNN_OK;
+    }
+    int after_step(int i) override {
+        if ((i + 1) % every != 0 && i + 1 != iterations) return GNN_OK;
+        return point(i / every);
+    }
+    int after_chunk(int i_end) override {
+        for (gnn_mlp *h : g->m) TRY_LAUNCHES(h);
+        return i_end == iterations ? readbacks() : GNN_OK; // (in front of the loop's own wait for the stream)
+    }
+};
+} // namespace
+
+extern "C" {
+
+int gnn_mlp_group_train_sampled_held_out(gnn_mlp_group_t *g, gnn_sampler_t *const *samplers, int iterations, const int32_t *batches,
+                                         const double *steps, const double *momenta, int noise, int every, int64_t held_rows, int rule,
+                                         int64_t *point_hits, double *point_loss, int64_t *ensemble_hits, int32_t *best_point,
+                                         double *best_weights) { return guarded([&]() -> int {
+    TRY(check_group(g));
+    TRY(check_per_member(g, steps, momenta));
+    const int K = g->K;
+    gnn_mlp *h0 = g->m[0];
+    if (!samplers) return fail(GNN_ERR_BAD_ARG, "samplers is null");
+    if (!batches) return fail(GNN_ERR_BAD_ARG, "batches is null: one batch size per member");
+    for (int k = 0; k < K; k++) if (!samplers[k]) return fail(GNN_ERR_BAD_ARG, "null sampler");
+    for (int k = 0; k < K; k++)
+        for (int j = 0; j < k; j++)
+            if (samplers[j] == samplers[k]) return fail(GNN_ERR_BAD_ARG, "the same sampler for two members: every member draws from its own");
+    for (int k = 0; k < K; k++) TRY(train_sampled_checks(g->m[k], samplers[k], iterations, batches[k], steps[k], noise));
+    TRY(check_held_out_args(h0, every, held_rows, rule, point_hits, point_loss, best_point));
+    for (gnn_mlp *h : g->m) TRY(check_handle(h)); // (a member's deferred host-batch update is applied first)
+    const int P = gnn_mlp_held_out_points(iterations, every);
+    for (gnn_mlp *h : g->m) TRY(ensure_keep_best(h, P));
+    TRY(prepare_group_point(g, held_rows));
+    GroupHeldOut obs;
+    obs.g = g; obs.iterations = iterations; obs.every = every; obs.rule = rule; obs.P = P; obs.held_rows = held_rows;
+    const size_t res_b = sizeof(unsigned long long) * obs.words() * (size_t)P;
+    const size_t need = res_b + sizeof(double) * (size_t)group_point_slots(g, held_rows);
+    if (g->held_res_bytes < need) {
+        HIP_TRY(hipStreamSynchronize(g->stream));
+        if (g->held_res) (void)hipFree(g->held_res);
+        g->held_res = nullptr; g->held_res_bytes = 0;
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&g->held_res), need));
+        g->held_res_bytes = need;
+    }
+    HIP_TRY(hipMemsetAsync(g->held_res, 0, res_b, h0->stream));
+    obs.d_res = reinterpret_cast<unsigned long long *>(g->held_res);
+    obs.d_slots = reinterpret_cast<double *>(g->held_res + res_b);
+    obs.want_weights = best_weights != nullptr;
+    obs.res.assign(obs.words() * (size_t)P, 0);
+    obs.best.assign((size_t)K, KeepBestRecord{0, 0.0, -1, 0});
+    if (best_weights) obs.w.assign((size_t)K * (size_t)h0->n_pad, 0.f);
+    g->each_grouped = g->each_mixed = 0;
+    if (K == 1 || !g->grouped) { // interval by interval, member after member, each with its own sampler and batch size through its own handle
+        for (int p = 0; p < P; p++) {
+            const int n_it = std::min(every, iterations - p * every);
+            for (int k = 0; k < K; k++) TRY(gnn_mlp_train_sampled(g->m[(size_t)k], samplers[k], n_it, batches[k], steps[k], momenta[k], noise));
+            TRY(obs.point(p));
+        }
+        for (gnn_mlp *h : g->m) TRY_LAUNCHES(h);
+        TRY(obs.readbacks());
+        HIP_TRY(hipStreamSynchronize(h0->stream));
+        g->each_mixed = iterations;
+    } else {
+        TRY(enter_grouped(g));
+        GroupLaunch gl;
+        TRY(group_launch(g, steps, momenta, &gl));
+        gl.sized = true;
+        SizedMembers each;
+        each.g = g; each.gl = &gl; each.track = g->sizes;
+        int nominal[GROUP_MAX];
+        for (int k = 0; k < K; k++) nominal[k] = batches[k];
+        const int t0 = h0->time;
+        int rc;
+        {
+            GroupScope scope(h0, &gl);
+            rc = train_sampled_run_each(h0, samplers, K, iterations, nominal, steps[0], momenta[0], noise, &obs, &each);
+        }
+        const int done = h0->time - t0;
+        leave_grouped(g, done, nullptr, 0, &each.track);
+        g->each_grouped = done;
+        TRY(rc);
+        // (the loop has waited for the stream behind the readbacks: the ONE synchronisation)
+    }
+    static_assert(sizeof(unsigned long long) == sizeof(double), "one buffer for counters and sums");
+    for (int p = 0; p < P; p++) {
+        const unsigned long long *row = obs.res.data() + (size_t)p * obs.words();
+        for (int k = 0; k < K; k++) {
+            point_hits[(size_t)p * K + k] = (int64_t)row[k];
+            std::memcpy(&point_loss[(size_t)p * K + k], &row[K + 1 + k], sizeof(double));
+        }
+        if (ensemble_hits) ensemble_hits[p] = (int64_t)row[K];
+    }
+    for (int k = 0; k < K; k++) {
+        best_point[k] = obs.best[(size_t)k].at;
+        if (best_weights && best_point[k] >= 0) {
+            const std::vector<float> wk(obs.w.begin() + (size_t)k * h0->n_pad, obs.w.begin() + (size_t)(k + 1) * h0->n_pad);
+            unpack_params(h0, wk, best_weights + (size_t)k * h0->n_params);
+        }
     }
     return GNN_OK;
 }); }

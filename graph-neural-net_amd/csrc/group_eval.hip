@@ -67,14 +67,14 @@ int ensure_workspace(gnn_mlp_group *g, int rows) {
     return GNN_OK;
 }
 
-// what both forms of the forward kernel take: the block's rows [first, first + B) of the data set, the net, the LDS plan
-GroupEvalParams forward_params(const gnn_mlp_group *g, int64_t first, int B) {
+// what both forms of the forward kernel take: the block's rows [first, first + B) of the resident set, the net, the LDS plan
+GroupEvalParams forward_params(const gnn_mlp_group *g, const ResidentSet &rs, int64_t first, int B) {
     const gnn_mlp *h0 = g->m[0];
     const int Lm = h0->L - 1;
     const bool bf = h0->dtype == GNN_DTYPE_BF16;
     GroupEvalParams p{};
-    p.X = bf ? static_cast<const void *>(h0->DXb + (size_t)first * h0->ld[0]) : static_cast<const void *>(h0->DX + (size_t)first * h0->ld[0]);
-    p.Y = h0->DY + (size_t)first * h0->ld[Lm]; p.ldy = h0->ld[Lm];
+    p.X = bf ? static_cast<const void *>(rs.Xb + (size_t)first * h0->ld[0]) : static_cast<const void *>(rs.X + (size_t)first * h0->ld[0]);
+    p.Y = rs.Y + (size_t)first * h0->ld[Lm]; p.ldy = h0->ld[Lm];
     p.W = bf ? static_cast<const void *>(h0->Wb) : static_cast<const void *>(h0->W);
     p.S = g->S;
     p.rows = B; p.L = h0->L;
@@ -94,14 +94,22 @@ struct EvalOut { // device results of one call
     int32_t *member_labels = nullptr;                      // [K][n] or null (with confusion only)
 };
 
-// rows [first, first + n) in blocks: forward (grouped or member after member), then the combine kernel
-int run_blocks(gnn_mlp_group *g, int64_t first, int64_t n, const EvalOut &o) {
+// which form a pass over n rows takes, and its block size
+struct BlockForm { bool grouped; int block; };
+BlockForm block_form(const gnn_mlp_group *g, int64_t n) {
+    const gnn_mlp *h0 = g->m[0];
+    const int cap = block_cap(h0);
+    const bool grouped = g->eval_plan.ok && (h0->dtype == GNN_DTYPE_BF16 || std::min<int64_t>(cap, n) <= kGroupedMaxBlockRowsF32);
+    return BlockForm{grouped, grouped ? (int)std::min<int64_t>(cap, n) : eval_block_rows(h0, n)};
+}
+
+// rows [first, first + n) of `rs` in blocks: forward (grouped or member after member), then the combine kernel
+int run_blocks(gnn_mlp_group *g, const ResidentSet &rs, int64_t first, int64_t n, const EvalOut &o) {
     gnn_mlp *h0 = g->m[0];
     const int Lm = h0->L - 1, ldo = h0->ld[Lm], d_out = h0->dims[Lm];
-    const bool bf = h0->dtype == GNN_DTYPE_BF16;
-    const int cap = block_cap(h0);
-    const bool grouped = g->eval_plan.ok && (bf || std::min<int64_t>(cap, n) <= kGroupedMaxBlockRowsF32);
-    const int block = grouped ? (int)std::min<int64_t>(cap, n) : eval_block_rows(h0, n);
+    const BlockForm form = block_form(g, n);
+    const bool grouped = form.grouped;
+    const int block = form.block;
     std::vector<std::unique_ptr<EvalScope>> scopes;
     if (grouped) {
         TRY(ensure_workspace(g, block));
@@ -117,10 +125,10 @@ int run_blocks(gnn_mlp_group *g, int64_t first, int64_t n, const EvalOut &o) {
     int slot = 0;
     for (int64_t off = 0; off < n; off += block) {
         const int B = (int)std::min<int64_t>(block, n - off);
-        const float *y = h0->DY + (size_t)(first + off) * ldo;
+        const float *y = rs.Y + (size_t)(first + off) * ldo;
         if (grouped) {
             const size_t cap_rows = (size_t)g->eval_ws_rows;
-            GroupEvalParams p = forward_params(g, first + off, B);
+            GroupEvalParams p = forward_params(g, rs, first + off, B);
             p.out = g->eval_ws; p.loss = g->eval_ws + cap_rows * 16;
             p.label = reinterpret_cast<int32_t *>(g->eval_ws + cap_rows * 17);
             p.ws_stride = cap_rows * 18;
@@ -138,7 +146,7 @@ int run_blocks(gnn_mlp_group *g, int64_t first, int64_t n, const EvalOut &o) {
         } else {
             for (int k = 0; k < g->K; k++) {
                 gnn_mlp *h = g->m[(size_t)k];
-                do_forward(h, h->DX + (size_t)(first + off) * h->ld[0], y, B, true, true, true);
+                do_forward(h, rs.X + (size_t)(first + off) * h->ld[0], y, B, true, true, true);
                 TRY_LAUNCHES(h);
                 cp.out[k] = h->prob; cp.loss[k] = h->lossv; cp.label[k] = h->labels;
             }
@@ -171,14 +179,11 @@ int n_slots_for(const gnn_mlp_group *g, int64_t n) { // an upper bound over both
     return (int)((n + block - 1) / block + (n + 255) / 256 + 1);
 }
 
-int check_eval_args(gnn_mlp_group *g, int64_t first, int64_t n) {
+int check_eval_args(gnn_mlp_group *g, int set, int64_t first, int64_t n) {
     if (!g) return fail(GNN_ERR_BAD_ARG, "null group");
     HIP_TRY(hipSetDevice(g->device));
     for (gnn_mlp *h : g->m) TRY(check_handle(h)); // (a member's deferred host-batch update is applied first)
-    const gnn_mlp *h0 = g->m[0];
-    if (!h0->DX) return fail(GNN_ERR_STATE, "no dataset uploaded");
-    if (n <= 0 || first < 0 || first + n > h0->dataset_n) return fail(GNN_ERR_BAD_ARG, "rows outside the dataset");
-    return GNN_OK;
+    return check_set_rows(g->m[0], set, first, n);
 }
 
 } // namespace
@@ -208,7 +213,7 @@ int enqueue_group_validation(gnn_mlp_group *g, int n, float *loss_rows, int64_t 
     const int R = 16 * g->eval_plan.mt;
     for (int off = 0; off < n; off += block) {
         const int B = std::min(block, n - off);
-        GroupEvalParams p = forward_params(g, off, B);
+        GroupEvalParams p = forward_params(g, resident_set(h0, GNN_SET_TRAIN), off, B);
         p.loss = loss_rows + off; p.loss_stride = (unsigned)stride;
         void *args[] = {&p};
         HIP_TRY(hipLaunchKernel(g->eval_plan.fn_loss, dim3((unsigned)((B + R - 1) / R), (unsigned)g->K), dim3(GE_NT), args,
@@ -227,6 +232,28 @@ int enqueue_group_curve_sum(gnn_mlp_group *g, const float *rows, int n_rows, int
 void free_group_eval(gnn_mlp_group *g) {
     if (g->eval_ws) (void)hipFree(g->eval_ws);
     g->eval_ws = nullptr; g->eval_ws_rows = 0;
+    if (g->held_res) (void)hipFree(g->held_res);
+    g->held_res = nullptr; g->held_res_bytes = 0;
+}
+
+// A point of the held-out curve (group.hip): gnn_mlp_group_evaluate_set_range's launches over rows [0, n) of the held-out set with
+// the results left on the device.  prepare_group_point grows what those launches need -- the group's workspace, or every
+// member's evaluation workspace -- so that a point between two steps allocates nothing and waits for nothing.
+int group_point_slots(const gnn_mlp_group *g, int64_t n) { return n_slots_for(g, n) * GE_GROUP_MAX; }
+int prepare_group_point(gnn_mlp_group *g, int64_t n) {
+    const BlockForm form = block_form(g, n);
+    if (form.grouped) return ensure_workspace(g, form.block);
+    for (gnn_mlp *h : g->m) {
+        int rc = GNN_OK;
+        EvalScope scope(h, form.block, &rc);
+        if (rc != GNN_OK) return rc;
+    }
+    return GNN_OK;
+}
+int enqueue_group_point(gnn_mlp_group *g, int64_t n, unsigned long long *d_hits, double *d_sums, double *d_slots) {
+    EvalOut o{};
+    o.hits = d_hits; o.sums = d_sums; o.slots = d_slots;
+    return run_blocks(g, resident_set(g->m[0], GNN_SET_HELD_OUT), 0, n, o);
 }
 
 } // namespace host
@@ -237,10 +264,24 @@ extern "C" {
 int gnn_mlp_group_eval_launches(const gnn_mlp_group_t *g) { return !g ? -1 : g->eval_plan.ok ? 2 : 0; }
 
 int gnn_mlp_group_evaluate_range(gnn_mlp_group_t *g, int64_t first, int64_t n, int64_t *member_hits, double *member_loss_sum,
-                                 int64_t *ensemble_hits) { return guarded([&]() -> int {
+                                 int64_t *ensemble_hits) {
+    return gnn_mlp_group_evaluate_set_range(g, GNN_SET_TRAIN, first, n, member_hits, member_loss_sum, ensemble_hits);
+}
+int gnn_mlp_group_ensemble_range(gnn_mlp_group_t *g, int64_t first, int64_t n, double *mean_out, int32_t *labels) {
+    return gnn_mlp_group_ensemble_set_range(g, GNN_SET_TRAIN, first, n, mean_out, labels);
+}
+int gnn_mlp_group_confusion_range(gnn_mlp_group_t *g, int64_t first, int64_t n, int64_t *member_confusion,
+                                  int64_t *ensemble_confusion, int32_t *member_labels) {
+    return gnn_mlp_group_confusion_set_range(g, GNN_SET_TRAIN, first, n, member_confusion, ensemble_confusion, member_labels);
+}
+
+// the three passes on either resident set of the group (MT:159-197: testOnTrainingData / testOnTestData)
+int gnn_mlp_group_evaluate_set_range(gnn_mlp_group_t *g, int set, int64_t first, int64_t n, int64_t *member_hits, double *member_loss_sum,
+                                     int64_t *ensemble_hits) { return guarded([&]() -> int {
     if (!g) return fail(GNN_ERR_BAD_ARG, "null group");
     if (!member_hits && !member_loss_sum && !ensemble_hits) return fail(GNN_ERR_BAD_ARG, "every output is null");
-    TRY(check_eval_args(g, first, n));
+    TRY(check_eval_args(g, set, first, n));
+    const ResidentSet rs = resident_set(g->m[0], set);
     const int K = g->K, ns = n_slots_for(g, n);
     // [K + 1] hit counters, [K] loss sums (one readback), then the loss slots
     const size_t head = sizeof(unsigned long long) * (size_t)(K + 1) + sizeof(double) * (size_t)K;
@@ -252,7 +293,7 @@ int gnn_mlp_group_evaluate_range(gnn_mlp_group_t *g, int64_t first, int64_t n, i
     o.hits = res.as<unsigned long long>();
     o.sums = reinterpret_cast<double *>(o.hits + (K + 1));
     o.slots = o.sums + K;
-    TRY(run_blocks(g, first, n, o));
+    TRY(run_blocks(g, rs, first, n, o));
     std::vector<unsigned long long> host((size_t)(2 * K + 1));
     static_assert(sizeof(unsigned long long) == sizeof(double), "one buffer for counters and sums");
     HIP_TRY(hipMemcpyAsync(host.data(), res.p, head, hipMemcpyDeviceToHost, st));
@@ -265,10 +306,11 @@ int gnn_mlp_group_evaluate_range(gnn_mlp_group_t *g, int64_t first, int64_t n, i
     return GNN_OK;
 }); }
 
-int gnn_mlp_group_ensemble_range(gnn_mlp_group_t *g, int64_t first, int64_t n, double *mean_out, int32_t *labels) { return guarded([&]() -> int {
+int gnn_mlp_group_ensemble_set_range(gnn_mlp_group_t *g, int set, int64_t first, int64_t n, double *mean_out, int32_t *labels) { return guarded([&]() -> int {
     if (!g) return fail(GNN_ERR_BAD_ARG, "null group");
     if (!mean_out && !labels) return fail(GNN_ERR_BAD_ARG, "every output is null");
-    TRY(check_eval_args(g, first, n));
+    TRY(check_eval_args(g, set, first, n));
+    const ResidentSet rs = resident_set(g->m[0], set);
     const gnn_mlp *h0 = g->m[0];
     const int K = g->K, ns = n_slots_for(g, n), d_out = h0->dims[h0->L - 1];
     const size_t head = sizeof(unsigned long long) * (size_t)(K + 1) + sizeof(double) * (size_t)K;
@@ -284,7 +326,7 @@ int gnn_mlp_group_ensemble_range(gnn_mlp_group_t *g, int64_t first, int64_t n, d
     o.slots = o.sums + K;
     o.mean = reinterpret_cast<float *>(res.as<char>() + head + slots_b);
     o.ens_label = reinterpret_cast<int32_t *>(res.as<char>() + head + slots_b + mean_b);
-    TRY(run_blocks(g, first, n, o));
+    TRY(run_blocks(g, rs, first, n, o));
     std::vector<char> host(mean_b + lab_b); // (one readback: the mean rows and the labels lie side by side)
     HIP_TRY(hipMemcpyAsync(host.data(), o.mean, mean_b + lab_b, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -296,11 +338,12 @@ int gnn_mlp_group_ensemble_range(gnn_mlp_group_t *g, int64_t first, int64_t n, d
     return GNN_OK;
 }); }
 
-int gnn_mlp_group_confusion_range(gnn_mlp_group_t *g, int64_t first, int64_t n, int64_t *member_confusion,
-                                  int64_t *ensemble_confusion, int32_t *member_labels) { return guarded([&]() -> int {
+int gnn_mlp_group_confusion_set_range(gnn_mlp_group_t *g, int set, int64_t first, int64_t n, int64_t *member_confusion,
+                                      int64_t *ensemble_confusion, int32_t *member_labels) { return guarded([&]() -> int {
     if (!g) return fail(GNN_ERR_BAD_ARG, "null group");
     if (!member_confusion && !ensemble_confusion && !member_labels) return fail(GNN_ERR_BAD_ARG, "every output is null");
-    TRY(check_eval_args(g, first, n));
+    TRY(check_eval_args(g, set, first, n));
+    const ResidentSet rs = resident_set(g->m[0], set);
     const gnn_mlp *h0 = g->m[0];
     const int K = g->K, ns = n_slots_for(g, n), d_out = h0->dims[h0->L - 1];
     const size_t cells = (size_t)d_out * d_out;
@@ -321,7 +364,7 @@ int gnn_mlp_group_confusion_range(gnn_mlp_group_t *g, int64_t first, int64_t n, 
     o.confusion = reinterpret_cast<unsigned long long *>(res.as<char>() + slots_b + head);
     o.member_labels = member_labels ? reinterpret_cast<int32_t *>(res.as<char>() + slots_b + head + conf_b) : nullptr;
     o.ens_label = reinterpret_cast<int32_t *>(res.as<char>() + slots_b + head + conf_b + lab_b);
-    TRY(run_blocks(g, first, n, o));
+    TRY(run_blocks(g, rs, first, n, o));
     std::vector<unsigned long long> host((conf_b + lab_b + 7) / 8);
     HIP_TRY(hipMemcpyAsync(host.data(), o.confusion, conf_b + lab_b, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));

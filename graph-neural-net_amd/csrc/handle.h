@@ -14,6 +14,7 @@
 #include "group_eval_kernel.h"
 #include "kernels.h"
 #include "eval_kernels.h"
+#include "keep_best_kernel.h"
 #include "lookahead.h"
 #include "group_sizes.h"
 #include "timer_slots.h"
@@ -53,6 +54,13 @@ struct GroupLaunch {
 } // namespace host
 } // namespace gnn
 
+namespace gnn {
+namespace host {
+// A resident set: A_0 = f(x) rows [n + PAD][ld[0]], expected rows [n + PAD][ld[L-1]], the bf16 shadow of the inputs (bf16 handles)
+struct ResidentSet { float *X = nullptr, *Y = nullptr; __bf16 *Xb = nullptr; int64_t n = 0; };
+} // namespace host
+} // namespace gnn
+
 struct gnn_mlp {
     int device = 0;
     int L = 0;                 // layerDims.length
@@ -85,6 +93,13 @@ struct gnn_mlp {
     std::vector<__bf16 *> actb, deltab; // actb[l] l = 0..L-2, deltab[l] l = 1..L-1
     __bf16 *DXb = nullptr;              // dataset inputs
     int64_t dataset_n = 0;
+    // The HELD-OUT set (gnn_mlp_upload_held_out*; MT:159-172 reads it as the test rows): a second resident set of the same layout,
+    // read by the evaluation passes only -- no training path names it.  resident_set() below gives either set as one struct.
+    gnn::host::ResidentSet held;
+    bool shared_held = false; // `held` is member 0's (the group's one copy)
+    // gnn_mlp_train_sampled_held_out (keep_best_kernel.h): the weights at the best point so far and the running best's history,
+    // ordinary allocations made at the first call (never a slice of a group's arena), kept for later calls
+    float *best_W = nullptr; gnn::KeepBestRecord *best_hist = nullptr; int best_hist_cap = 0;
 
     hipStream_t stream = nullptr, own_stream = nullptr;
 
@@ -208,6 +223,9 @@ struct gnn_mlp_group {
     struct EvalPlan { bool ok = false; int mt = 0; gnn::GroupEvalLds lds{}; const void *fn = nullptr, *fn_loss = nullptr; } eval_plan; // (fn_loss: the LOSS_ONLY twin)
     float *eval_ws = nullptr;
     int eval_ws_rows = 0;
+    // gnn_mlp_group_train_sampled_held_out: [P][2K + 1] point results (K hit counters, the ensemble's, K loss sums) and the loss
+    // slots of one point's combine launches, made at the first call, grown on demand
+    char *held_res = nullptr; size_t held_res_bytes = 0;
     int64_t each_grouped = 0, each_mixed = 0; // of the last gnn_mlp_group_train_sampled_each / _sizes call: iterations by grouped launches / member after member
     gnn::host::GroupSizes sizes;  // member k's sizes of the batches member 0's look-ahead state names (group_sizes.h)
 };
@@ -216,6 +234,11 @@ namespace gnn {
 namespace host {
 
 // ---- group_eval.hip ------------------------------------------------------------------------------
+// gnn_mlp_group_evaluate_set_range's passes for the held-out curve (group.hip), enqueued only: rows [0, n) of the held-out set,
+// the K + 1 hit counters to d_hits (zeroed by the caller), the K loss sums to d_sums, through d_slots (group_point_slots(g, n) doubles)
+int group_point_slots(const gnn_mlp_group *g, int64_t n);
+int prepare_group_point(gnn_mlp_group *g, int64_t n); // the workspaces a point needs, made before the first step
+int enqueue_group_point(gnn_mlp_group *g, int64_t n, unsigned long long *d_hits, double *d_sums, double *d_slots);
 void plan_group_eval(gnn_mlp_group *g); // at create: does group_forward_kernel apply to the group's net?
 void free_group_eval(gnn_mlp_group *g);
 // The validation pass of a group's observed training loop (needs eval_plan.ok; enqueues on member 0's stream, allocates nothing,
@@ -233,6 +256,17 @@ int check_batch(const gnn_mlp *h, int B);
 int check_range(const gnn_mlp *h, int64_t first, int B);
 int check_step_args(gnn_mlp *h, int B, double step, int noise);
 int get_flat(gnn_mlp *h, const float *dev, double *flat);
+void unpack_params(const gnn_mlp *h, const std::vector<float> &in, double *flat);
+// the training set or the held-out set of a handle (GNN_SET_*), as the evaluation passes read them
+inline ResidentSet resident_set(const gnn_mlp *h, int set) {
+    return set == GNN_SET_HELD_OUT ? h->held : ResidentSet{h->DX, h->DY, h->DXb, h->dataset_n};
+}
+// ... and the status for a `set` that is neither, a set never uploaded, rows outside it
+int check_set_rows(const gnn_mlp *h, int set, int64_t first, int64_t n);
+// gnn_mlp_evaluate_set_range's block loop, enqueued only (abi.hip): hits and the loss sum of rows [first, first + n) of `rs` into
+// *d_hits / *d_loss (device; d_hits zeroed by the caller), the confusion launch when cf_counts is given
+int enqueue_evaluation(gnn_mlp *h, const ResidentSet &rs, int64_t first, int64_t n, unsigned long long *d_hits, double *d_loss,
+                       unsigned long long *cf_counts, int32_t *labels_out);
 int set_flat(gnn_mlp *h, float *dev, const double *flat);
 
 #define HIP_TRY(expr)                                                                         \
@@ -448,8 +482,8 @@ int step_on_device_indices(gnn_mlp *h, const int32_t *d_idx, int B, double step,
 int create_handle(const int32_t *dims, int n_dims, int out_kind, int inner_act, int last_act, int loss, int64_t seed, int dtype,
                   int device, int max_batch, hipStream_t shared_stream, gnn_mlp **out);
 void destroy_handle(gnn_mlp *h);
-int upload_dataset_f64(gnn_mlp *h, const double *X, const double *Y, int64_t N);
-int upload_dataset_u8(gnn_mlp *h, const uint8_t *pixels, const uint8_t *labels, int64_t N);
+int upload_dataset_f64(gnn_mlp *h, const double *X, const double *Y, int64_t N, int set = GNN_SET_TRAIN);
+int upload_dataset_u8(gnn_mlp *h, const uint8_t *pixels, const uint8_t *labels, int64_t N, int set = GNN_SET_TRAIN);
 int train_range_checks(gnn_mlp *h, int64_t first, int B, int n_steps, double step);
 int train_range_steps(gnn_mlp *h, int64_t first, int B, int s, int n_steps, double step, double momentum);
 int train_sampled_checks(gnn_mlp *h, gnn_sampler_t *s, int iterations, int batch, double step, int noise);
@@ -480,6 +514,12 @@ struct SampledEach {
 // batches[m]: sampler m's nominal batch size (all equal unless each->sized()); every ring has the slot stride of the largest
 int train_sampled_run_each(gnn_mlp *h, gnn_sampler_t *const *samplers, int n, int iterations, const int *batches, double step,
                            double momentum, int noise, SampledObserver *obs, SampledEach *each);
+// the held-out curve (sampler.hip; keep_best_kernel.h): a handle's snapshot buffer and history for `points` points, the launch for
+// K nets of one shape, the arguments both entry points refuse
+int ensure_keep_best(gnn_mlp *h, int points);
+int launch_keep_best(hipStream_t stream, gnn_mlp *const *m, int K, const unsigned long long *hits, const double *loss, int point, int rule);
+int check_held_out_args(const gnn_mlp *h, int every, int64_t held_rows, int rule, const void *point_hits, const void *point_loss,
+                        const void *best_point);
 gnn_sampler_t *sampler_copy(const gnn_sampler_t *s);
 void sampler_assign(gnn_sampler_t *dst, const gnn_sampler_t *src);
 

@@ -228,6 +228,8 @@ bool use_tail(const gnn_mlp *h) {
 // bf16 twin of an A_0 row pointer: the staging rows or the resident dataset
 const __bf16 *a0_bf16(const gnn_mlp *h, const float *a0) {
     if (a0 == h->act[0]) return h->actb[0];
+    // (a row of the held-out set: the evaluation passes alone read it)
+    if (h->held.X && a0 >= h->held.X && a0 < h->held.X + ((size_t)h->held.n + PAD) * h->ld[0]) return h->held.Xb + (a0 - h->held.X);
     return h->DXb + (a0 - h->DX);
 }
 

@@ -330,6 +330,116 @@ int gnn::host::train_sampled_run_each(gnn_mlp *h, gnn_sampler_t *const *samplers
     return train_sampled_impl(h, samplers, n, iterations, batches, step, momentum, noise, obs, each);
 }
 
+// ---- the held-out curve and the best weights (keep_best_kernel.h) --------------------------------------------------------------
+// A handle's snapshot buffer and its history of the running best: ordinary allocations made at the first call, kept for later
+// calls, freed with the handle.
+int gnn::host::ensure_keep_best(gnn_mlp *h, int points) {
+    if (!h->best_W) {
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&h->best_W), sizeof(float) * (size_t)h->n_pad));
+        HIP_TRY(hipMemsetAsync(h->best_W, 0, sizeof(float) * (size_t)h->n_pad, h->stream));
+    }
+    if (h->best_hist_cap < points) {
+        HIP_TRY(hipStreamSynchronize(h->stream)); // (nothing queued may still write the shorter history)
+        if (h->best_hist) (void)hipFree(h->best_hist);
+        h->best_hist = nullptr; h->best_hist_cap = 0;
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&h->best_hist), sizeof(KeepBestRecord) * (size_t)points));
+        h->best_hist_cap = points;
+    }
+    return GNN_OK;
+}
+// One launch for the K nets of m (one shape): point `point`'s results hits[k] / loss[k] against record point - 1 of each history
+int gnn::host::launch_keep_best(hipStream_t stream, gnn_mlp *const *m, int K, const unsigned long long *hits, const double *loss, int point, int rule) {
+    KeepBestParams kp{};
+    for (int k = 0; k < K; k++) { kp.W[k] = m[k]->W; kp.snap[k] = m[k]->best_W; kp.hist[k] = m[k]->best_hist; }
+    kp.hits = hits; kp.loss = loss;
+    kp.n4 = (unsigned)(m[0]->n_pad / 4);
+    kp.point = point; kp.rule = rule;
+    const unsigned per_block = KB_NT * KB_VEC;
+    hipLaunchKernelGGL(keep_best_kernel, dim3((kp.n4 + per_block - 1) / per_block, (unsigned)K), dim3(KB_NT), 0, stream, kp);
+    HIP_TRY(hipGetLastError());
+    return GNN_OK;
+}
+int gnn::host::check_held_out_args(const gnn_mlp *h, int every, int64_t held_rows, int rule, const void *point_hits, const void *point_loss,
+                                   const void *best_point) {
+    if (!point_hits || !point_loss || !best_point) return fail(GNN_ERR_BAD_ARG, "null output");
+    if (rule != GNN_BEST_LOSS && rule != GNN_BEST_HITS) return fail(GNN_ERR_BAD_ARG, "rule: GNN_BEST_LOSS or GNN_BEST_HITS");
+    if (every < 1) return fail(GNN_ERR_BAD_ARG, "every must be positive");
+    if (!h->held.X) return fail(GNN_ERR_STATE, "no held-out set uploaded");
+    if (held_rows < 1 || held_rows > h->held.n) return fail(GNN_ERR_BAD_ARG, "held_rows outside the held-out set");
+    return GNN_OK;
+}
+
+namespace {
+// Behind the iterations that end an interval: the pass of gnn_mlp_evaluate_set_range over the held-out rows with its results
+// left in slot p of d_res ([P][hits, loss sum]), then the keep_best launch.  Behind the last chunk, in front of the loop's own
+// wait for the stream: the readbacks.
+struct LoneHeldOut : SampledObserver {
+    gnn_mlp *h; int iterations, every, rule, P; int64_t held_rows;
+    unsigned long long *d_res;
+    bool want_weights;
+    std::vector<unsigned long long> res; KeepBestRecord best{0, 0.0, -1, 0}; std::vector<float> w;
+    int after_step(int i) override {
+        if ((i + 1) % every != 0 && i + 1 != iterations) return GNN_OK;
+        const int p = i / every;
+        unsigned long long *hits = d_res + 2 * (size_t)p;
+        double *loss = reinterpret_cast<double *>(hits + 1);
+        TRY(enqueue_evaluation(h, h->held, 0, held_rows, hits, loss, nullptr, nullptr));
+        return launch_keep_best(h->stream, &h, 1, hits, loss, p, rule);
+    }
+    int after_chunk(int i_end) override {
+        TRY_LAUNCHES(h);
+        if (i_end != iterations) return GNN_OK;
+        HIP_TRY(hipMemcpyAsync(res.data(), d_res, sizeof(unsigned long long) * res.size(), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(&best, h->best_hist + (P - 1), sizeof(KeepBestRecord), hipMemcpyDeviceToHost, h->stream));
+        if (want_weights) HIP_TRY(hipMemcpyAsync(w.data(), h->best_W, sizeof(float) * w.size(), hipMemcpyDeviceToHost, h->stream));
+        return GNN_OK;
+    }
+};
+} // namespace
+
+extern "C" {
+
+int gnn_mlp_held_out_points(int iterations, int every) {
+    if (iterations < 1 || every < 1) return -1;
+    return (int)(((int64_t)iterations + every - 1) / every);
+}
+
+int gnn_mlp_train_sampled_held_out(gnn_mlp_t *h, gnn_sampler_t *s, int iterations, int batch, double step, double momentum,
+                                   int noise, int every, int64_t held_rows, int rule, int64_t *point_hits, double *point_loss,
+                                   int32_t *best_point, double *best_weights) { return guarded([&]() -> int {
+    TRY(check_handle(h));
+    TRY(train_sampled_checks(h, s, iterations, batch, step, noise));
+    TRY(check_held_out_args(h, every, held_rows, rule, point_hits, point_loss, best_point));
+    const int P = gnn_mlp_held_out_points(iterations, every);
+    TRY(ensure_keep_best(h, P));
+    { // (the evaluation workspace a point may need, grown before the first step)
+        int rc_ws = GNN_OK;
+        EvalScope scope(h, eval_block_rows(h, held_rows), &rc_ws);
+        if (rc_ws != GNN_OK) return rc_ws;
+    }
+    DevScratch dres;
+    TRY(dres.alloc(sizeof(unsigned long long) * 2 * (size_t)P));
+    HIP_TRY(hipMemsetAsync(dres.p, 0, sizeof(unsigned long long) * 2 * (size_t)P, h->stream));
+    LoneHeldOut obs;
+    obs.h = h; obs.iterations = iterations; obs.every = every; obs.rule = rule; obs.P = P; obs.held_rows = held_rows;
+    obs.d_res = dres.as<unsigned long long>();
+    obs.want_weights = best_weights != nullptr;
+    obs.res.assign(2 * (size_t)P, 0);
+    if (best_weights) obs.w.assign((size_t)h->n_pad, 0.f);
+    TRY(train_sampled_impl(h, &s, 1, iterations, &batch, step, momentum, noise, &obs, nullptr));
+    // (the loop has waited for the stream behind the readbacks: the ONE synchronisation)
+    static_assert(sizeof(unsigned long long) == sizeof(double), "one buffer for counters and sums");
+    for (int p = 0; p < P; p++) {
+        point_hits[p] = (int64_t)obs.res[2 * (size_t)p];
+        std::memcpy(&point_loss[p], &obs.res[2 * (size_t)p + 1], sizeof(double));
+    }
+    *best_point = obs.best.at;
+    if (best_weights && obs.best.at >= 0) unpack_params(h, obs.w, best_weights);
+    return GNN_OK;
+}); }
+
+} // extern "C"
+
 namespace {
 // The observed variants (NNT:68-72, 75-79) of a lone handle: after iteration i the summed validation loss of rows
 // [0, validation_size) goes to d_val[i] (device).

@@ -43,6 +43,44 @@ def _dp(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
 
 
+SET_TRAIN, SET_HELD_OUT = 0, 1
+BEST_LOSS, BEST_HITS = 0, 1
+_RULES = {"loss": BEST_LOSS, "hits": BEST_HITS}
+
+
+def _rule(rule):
+    if isinstance(rule, str):
+        if rule not in _RULES:
+            raise ValueError("rule: 'loss' or 'hits', got %r" % (rule,))
+        return _RULES[rule]
+    return int(rule)
+
+
+def best_point(hits, loss, rule="loss"):
+    """The point of a held-out curve that train_sampled_held_out keeps (csrc/keep_best_kernel.h), on the host: the running best
+    starts as "none" and is decided in point order.  Point p becomes the best under "loss" when its loss is not NaN and (there
+    is no best yet, or its loss is strictly lower); under "hits" when there is no best yet, or it has strictly more hits, or
+    equal hits and a strictly lower loss (a NaN loss is never lower).  Ties keep the earlier point.  Returns the final best,
+    -1 when "loss" never saw a number."""
+    hits = np.asarray(hits).ravel()
+    loss = np.asarray(loss, dtype=np.float64).ravel()
+    if hits.size != loss.size:
+        raise ValueError("hits / loss: one value per point each")
+    rule = _rule(rule)
+    if rule not in (BEST_LOSS, BEST_HITS):
+        raise ValueError("rule: 'loss' or 'hits'")
+    at = -1
+    for p in range(loss.size):
+        h, l = int(hits[p]), float(loss[p])
+        if rule == BEST_LOSS:
+            better = not np.isnan(l) and (at < 0 or l < float(loss[at]))
+        else:
+            better = at < 0 or h > int(hits[at]) or (h == int(hits[at]) and l < float(loss[at]))
+        if better:
+            at = p
+    return at
+
+
 class NeuralNet:
     """NeuralNet.java:7-67 -- propagate / calculateLoss / calculateWeightGradient /
     gradientStep / getInputDim / getOutputDim, batched: a 2-D array is a batch of rows."""
@@ -200,6 +238,45 @@ class NeuralNet:
     def dataset_size(self):
         return self._lib.gnn_mlp_dataset_size(self._h)
 
+    # -- the held-out set (MNISTTrainer's test rows, MT:98, MT:159-172): a second resident set, read by evaluation only -----
+    def upload_held_out(self, X, Y):
+        X = _f64(X, self.layer_dims[0])
+        Y = _f64(Y, self.layer_dims[-1])
+        if X.shape[0] != Y.shape[0]:
+            raise ValueError("input / expected row counts differ")
+        _capi.check(self._lib.gnn_mlp_upload_held_out(self._h, _dp(X), _dp(Y), X.shape[0]))
+
+    def upload_held_out_u8(self, pixels, labels):
+        pixels = np.ascontiguousarray(pixels, dtype=np.uint8).reshape(-1, self.layer_dims[0])
+        labels = np.ascontiguousarray(labels, dtype=np.uint8).ravel()
+        if pixels.shape[0] != labels.size:
+            raise ValueError("pixel / label row counts differ")
+        u8 = C.POINTER(C.c_uint8)
+        _capi.check(self._lib.gnn_mlp_upload_held_out_u8(self._h, pixels.ctypes.data_as(u8),
+                                                         labels.ctypes.data_as(u8), labels.size))
+
+    @property
+    def held_out_size(self):
+        return self._lib.gnn_mlp_set_rows(self._h, SET_HELD_OUT)
+
+    def train_sampled_held_out(self, sampler, iterations, batch, step, momentum, every, held_rows=None, rule="loss", weights=True):
+        """train_sampled (NNT:82-90) with the held-out curve (testOnTestData, MT:159-172, along the run) and the best weights
+        kept on the device: after every `every` iterations, and after the last one, rows [0, held_rows) of the held-out set
+        (default: all) are evaluated.  Returns (hits[P], loss_sums[P], best_point, best_weights) -- best_point by `rule`
+        ("loss" or "hits": best_point()), best_weights the flat weights of get_weights() AT that point, or None with
+        weights=False or when best_point is -1."""
+        if held_rows is None:
+            held_rows = self.held_out_size
+        p = self._lib.gnn_mlp_held_out_points(int(iterations), int(every))
+        hits = np.zeros(max(p, 0), dtype=np.int64)
+        loss = np.zeros(max(p, 0), dtype=np.float64)
+        best = C.c_int32(-1)
+        w = np.empty(self.n_params) if weights else None
+        _capi.check(self._lib.gnn_mlp_train_sampled_held_out(
+            self._h, sampler._h, int(iterations), int(batch), float(step), float(momentum), 0, int(every), int(held_rows),
+            _rule(rule), hits.ctypes.data_as(C.POINTER(C.c_int64)), _dp(loss), C.byref(best), _dp(w) if weights else None))
+        return hits, loss, int(best.value), (w if weights and best.value >= 0 else None)
+
     def gradient_step_indexed(self, idx, step, momentum, noise=False):
         idx = np.ascontiguousarray(idx, dtype=np.int32).ravel()
         _capi.check(self._lib.gnn_mlp_gradient_step_indexed(
@@ -225,47 +302,53 @@ class NeuralNet:
                                                    out.ctypes.data_as(C.POINTER(C.c_int32))))
         return out
 
-    def count_hits_range(self, first=0, n=None):
+    def count_hits_range(self, first=0, n=None, held_out=False):
         """testOnTrainingData / testOnTestData (MT:159-197) over dataset rows [first, first + n): the number of rows whose `>=`
-        argmax equals the expected class (the last index whose expected value is 1); one readback."""
+        argmax equals the expected class (the last index whose expected value is 1); one readback.  held_out=True: rows of
+        the held-out set (MT:159-172)."""
+        if held_out:
+            return self.evaluate_range(first, n, held_out=True)[0]
         n = self.dataset_size - int(first) if n is None else int(n)
         out = C.c_int64()
         _capi.check(self._lib.gnn_mlp_count_hits_range(self._h, int(first), n, C.byref(out)))
         return out.value
 
     # the same pass with what it has on the device returned: gnn_mlp_evaluate_range (one call, one readback, any n)
-    def _rows(self, first, n):
+    def _rows(self, first, n, held_out=False):
         first = int(first)
         if n is None:
-            size = self.dataset_size
+            size = self.held_out_size if held_out else self.dataset_size
             if size <= 0:
                 raise ValueError("n=None needs an uploaded data set")
             n = size - first
         return first, int(n)
 
-    def evaluate_range(self, first=0, n=None):
+    def evaluate_range(self, first=0, n=None, held_out=False):
         """(hits, loss_sum) over dataset rows [first, first + n): count_hits_range's count (MT:159-197) and the sum of
-        calculateLoss over the rows (validate(), NNT:102-113, without its division)."""
-        first, n = self._rows(first, n)
+        calculateLoss over the rows (validate(), NNT:102-113, without its division).  held_out=True (here and in
+        confusion_range / labels_range): rows of the held-out set (testOnTestData, MT:159-172)."""
+        first, n = self._rows(first, n, held_out)
         hits, loss = C.c_int64(), C.c_double()
-        _capi.check(self._lib.gnn_mlp_evaluate_range(self._h, first, n, C.byref(hits), C.byref(loss), None, None))
+        _capi.check(self._lib.gnn_mlp_evaluate_set_range(self._h, int(bool(held_out)), first, n, C.byref(hits), C.byref(loss), None, None))
         return hits.value, loss.value
 
-    def confusion_range(self, first=0, n=None):
+    def confusion_range(self, first=0, n=None, held_out=False):
         """The confusion matrix of the rows, (d_out, d_out) int64: entry [e, p] counts the rows whose expected class (the last
         index whose expected value is 1, MT:186-188) is e and whose `>=` argmax (MT:166-168) is p.  Exact; its trace is
         count_hits_range's count."""
-        first, n = self._rows(first, n)
+        first, n = self._rows(first, n, held_out)
         d = self.layer_dims[-1]
         conf = np.zeros((d, d), dtype=np.int64)
-        _capi.check(self._lib.gnn_mlp_evaluate_range(self._h, first, n, None, None, conf.ctypes.data_as(C.POINTER(C.c_int64)), None))
+        _capi.check(self._lib.gnn_mlp_evaluate_set_range(self._h, int(bool(held_out)), first, n, None, None,
+                                                         conf.ctypes.data_as(C.POINTER(C.c_int64)), None))
         return conf
 
-    def labels_range(self, first=0, n=None):
+    def labels_range(self, first=0, n=None, held_out=False):
         """argmax_range for any number of rows: int32[n], the labels count_hits_range and confusion_range count."""
-        first, n = self._rows(first, n)
+        first, n = self._rows(first, n, held_out)
         lab = np.empty(max(n, 0), dtype=np.int32)
-        _capi.check(self._lib.gnn_mlp_evaluate_range(self._h, first, n, None, None, None, lab.ctypes.data_as(C.POINTER(C.c_int32))))
+        _capi.check(self._lib.gnn_mlp_evaluate_set_range(self._h, int(bool(held_out)), first, n, None, None, None,
+                                                         lab.ctypes.data_as(C.POINTER(C.c_int32))))
         return lab
 
     # -- which inputs the loss depends on: csrc/input_grad_kernel.h ----------------------------------
@@ -474,6 +557,8 @@ class NetGroup:
                                                    dtype, device, max_batch, C.byref(self._h)))
         self.layer_dims, self.seeds, self.max_batch = dims, sd, max_batch
         self._dataset_rows = None
+        self._held_out_rows = None
+        self.n_params = sum(dims[l] * dims[l + 1] for l in range(len(dims) - 1))
         self.members = []
         for k in range(len(sd)):
             h = C.c_void_p()
@@ -513,6 +598,57 @@ class NetGroup:
         _capi.check(self._lib.gnn_mlp_group_upload_dataset_u8(self._h, pixels.ctypes.data_as(u8),
                                                               labels.ctypes.data_as(u8), labels.size))
         self._dataset_rows = labels.size
+
+    # the group's held-out set (MT:98, MT:159-172): ONE copy, seen by every member
+    def upload_held_out(self, X, Y):
+        X = _f64(X, self.layer_dims[0])
+        Y = _f64(Y, self.layer_dims[-1])
+        if X.shape[0] != Y.shape[0]:
+            raise ValueError("input / expected row counts differ")
+        _capi.check(self._lib.gnn_mlp_group_upload_held_out(self._h, _dp(X), _dp(Y), X.shape[0]))
+        self._held_out_rows = X.shape[0]
+
+    def upload_held_out_u8(self, pixels, labels):
+        pixels = np.ascontiguousarray(pixels, dtype=np.uint8).reshape(-1, self.layer_dims[0])
+        labels = np.ascontiguousarray(labels, dtype=np.uint8).ravel()
+        if pixels.shape[0] != labels.size:
+            raise ValueError("pixel / label row counts differ")
+        u8 = C.POINTER(C.c_uint8)
+        _capi.check(self._lib.gnn_mlp_group_upload_held_out_u8(self._h, pixels.ctypes.data_as(u8),
+                                                               labels.ctypes.data_as(u8), labels.size))
+        self._held_out_rows = labels.size
+
+    @property
+    def held_out_size(self):
+        return self.members[0].held_out_size
+
+    def train_sampled_held_out(self, samplers, iterations, batches, steps, momenta, every, held_rows=None, rule="loss", weights=True):
+        """train_sampled with one sampler and one batch size per member (a scalar `batches`: one size for all), the held-out
+        curves (MT:159-172 along the run) and every member's best weights kept on the device (NeuralNet.train_sampled_held_out).
+        Returns (hits[P, K], loss_sums[P, K], ensemble_hits[P], best_point[K], best_weights[K, num_params]) -- best_weights None
+        with weights=False; row k is unwritten where best_point[k] is -1."""
+        k = len(self)
+        st, mo = _per_member("steps", steps, k), _per_member("momenta", momenta, k)
+        each = self._samplers(samplers)
+        if each is None:
+            raise ValueError("samplers: one per member")
+        bs = [int(batches)] * k if np.ndim(batches) == 0 else [int(b) for b in batches]
+        if len(bs) != k:
+            raise ValueError("batches: one size per member (%d), got %d" % (k, len(bs)))
+        if held_rows is None:
+            held_rows = self.held_out_size
+        p = max(self._lib.gnn_mlp_held_out_points(int(iterations), int(every)), 0)
+        hits = np.zeros((p, k), dtype=np.int64)
+        loss = np.zeros((p, k), dtype=np.float64)
+        ens = np.zeros(p, dtype=np.int64)
+        best = np.full(k, -1, dtype=np.int32)
+        w = np.zeros((k, self.n_params)) if weights else None
+        i64 = C.POINTER(C.c_int64)
+        _capi.check(self._lib.gnn_mlp_group_train_sampled_held_out(
+            self._h, each, int(iterations), (C.c_int32 * k)(*bs), _dp(st), _dp(mo), 0, int(every), int(held_rows), _rule(rule),
+            hits.ctypes.data_as(i64), _dp(loss), ens.ctypes.data_as(i64), best.ctypes.data_as(C.POINTER(C.c_int32)),
+            _dp(w) if weights else None))
+        return hits, loss, ens, best, w
 
     def train_range(self, first, B, n_steps, steps, momenta):
         """NetGroup member k: train_range(first, B, n_steps, steps[k], momenta[k]); scalars apply to every member."""
@@ -612,53 +748,56 @@ class NetGroup:
         """2: one grouped forward launch + one combine launch per block of rows; 0: member after member."""
         return self._lib.gnn_mlp_group_eval_launches(self._h)
 
-    def _rows(self, first, n):
+    def _rows(self, first, n, held_out=False):
         first = int(first)
         if n is None:
-            if getattr(self, "_dataset_rows", None) is None:
+            rows = getattr(self, "_held_out_rows" if held_out else "_dataset_rows", None)
+            if rows is None:
                 raise ValueError("n=None needs an uploaded data set")
-            n = self._dataset_rows - first
+            n = rows - first
         return first, int(n)
 
-    def evaluate_range(self, first=0, n=None):
+    def evaluate_range(self, first=0, n=None, held_out=False):
         """(hits[K], loss_sums[K], ensemble_hits) over rows [first, first + n) of the group's data set: testOnTrainingData
         (MT:159-197) and the sum of calculateLoss (validate(), NNT:102-113, without its division) for every member, and the
-        hits of the ensemble's mean output."""
-        first, n = self._rows(first, n)
+        hits of the ensemble's mean output.  held_out=True (here, in the ensemble calls and in confusion_range): rows of the
+        group's held-out set (testOnTestData, MT:159-172)."""
+        first, n = self._rows(first, n, held_out)
         k = len(self)
         hits = np.zeros(k, dtype=np.int64)
         loss = np.zeros(k, dtype=np.float64)
         ens = C.c_int64(0)
-        _capi.check(self._lib.gnn_mlp_group_evaluate_range(self._h, first, n, hits.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                           _dp(loss), C.byref(ens)))
+        _capi.check(self._lib.gnn_mlp_group_evaluate_set_range(self._h, int(bool(held_out)), first, n,
+                                                               hits.ctypes.data_as(C.POINTER(C.c_int64)), _dp(loss), C.byref(ens)))
         return hits, loss, int(ens.value)
 
-    def ensemble_propagate_range(self, first, n):
+    def ensemble_propagate_range(self, first, n, held_out=False):
         """The mean of the members' propagate() over the rows: n x d_out (fp64 of the f32 mean, taken in member order)."""
-        first, n = self._rows(first, n)
+        first, n = self._rows(first, n, held_out)
         out = np.empty((max(n, 0), self.layer_dims[-1]), dtype=np.float64)
-        _capi.check(self._lib.gnn_mlp_group_ensemble_range(self._h, first, n, _dp(out), None))
+        _capi.check(self._lib.gnn_mlp_group_ensemble_set_range(self._h, int(bool(held_out)), first, n, _dp(out), None))
         return out
 
-    def ensemble_argmax_range(self, first, n):
+    def ensemble_argmax_range(self, first, n, held_out=False):
         """argmax (MT:166-168) of the mean output, per row."""
-        first, n = self._rows(first, n)
+        first, n = self._rows(first, n, held_out)
         lab = np.empty(max(n, 0), dtype=np.int32)
-        _capi.check(self._lib.gnn_mlp_group_ensemble_range(self._h, first, n, None, lab.ctypes.data_as(C.POINTER(C.c_int32))))
+        _capi.check(self._lib.gnn_mlp_group_ensemble_set_range(self._h, int(bool(held_out)), first, n, None,
+                                                               lab.ctypes.data_as(C.POINTER(C.c_int32))))
         return lab
 
-    def confusion_range(self, first=0, n=None, labels=False):
+    def confusion_range(self, first=0, n=None, labels=False, held_out=False):
         """(member (K, d, d), ensemble (d, d)) int64 confusion matrices over the rows -- entry [e, p]: expected class e (MT:186-188),
         predicted class p, member k's `>=` argmax or the argmax of the mean output -- from the pass of evaluate_range and one
         readback; with labels=True also the members' labels (K, n) int32 the counts were made from."""
-        first, n = self._rows(first, n)
+        first, n = self._rows(first, n, held_out)
         k, d = len(self), self.layer_dims[-1]
         member = np.zeros((k, d, d), dtype=np.int64)
         ens = np.zeros((d, d), dtype=np.int64)
         lab = np.empty((k, max(n, 0)), dtype=np.int32) if labels else None
         i64 = C.POINTER(C.c_int64)
-        _capi.check(self._lib.gnn_mlp_group_confusion_range(
-            self._h, first, n, member.ctypes.data_as(i64), ens.ctypes.data_as(i64),
+        _capi.check(self._lib.gnn_mlp_group_confusion_set_range(
+            self._h, int(bool(held_out)), first, n, member.ctypes.data_as(i64), ens.ctypes.data_as(i64),
             lab.ctypes.data_as(C.POINTER(C.c_int32)) if labels else None))
         return (member, ens, lab) if labels else (member, ens)
 

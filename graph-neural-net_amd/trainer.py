@@ -48,12 +48,15 @@ class NeuralNetTrainer:
     """NeuralNetTrainer(Map<double[],double[]> data, NeuralNet net) (NNT:28-43): `data` is given as
     two row-aligned matrices (or raw uint8 pixels + labels); master order = row order."""
 
-    def __init__(self, data_x, data_y, net, raw_u8=False, seed=1):
+    def __init__(self, data_x, data_y, net, raw_u8=False, seed=1, held_out=None):
+        """held_out: (x, y), the test rows of MT:98 in the form of the training rows -- uploaded as the net's held-out set."""
         self.net = net
         if raw_u8:
             net.upload_dataset_u8(data_x, data_y)
         else:
             net.upload_dataset(data_x, data_y)
+        if held_out is not None:
+            (net.upload_held_out_u8 if raw_u8 else net.upload_held_out)(held_out[0], held_out[1])
         self.size = net.dataset_size
         self.sampler = Sampler(self.size, seed)       # random = new Random(1) (NNT:42)
 
@@ -100,6 +103,13 @@ class NeuralNetTrainer:
 
     OBSERVER_BURST = 256   # iterations per device loop when a progress monitor wants to be stepped
 
+    def log_run(self, path, net_dim, iterations, step, batch, momentum):
+        """MT:241: appends the run's row to `path` -- testOnTrainingData (MT:180-197) over the training set and testOnTestData
+        (MT:159-172) over the held-out set, both on the device, through train_log_row.  Returns (trainAcc, testAcc)."""
+        train_acc, test_acc = accuracy(self.net), accuracy(self.net, held_out=True)
+        log_test(path, net_dim, iterations, step, batch, momentum, False, train_acc, test_acc)
+        return train_acc, test_acc
+
     def train_stepwise(self, iterations, stepSize, batchSize, momentum, noise=False, observer=None):
         """The observed loop NNT:75-79 one ABI call per action (sample on the host, an indexed step, a validation readback per
         iteration) -- the form `train` had until round 4; kept for the tests that compare the device loop against it."""
@@ -123,12 +133,15 @@ class NetGroupTrainer:
 
     OBSERVER_BURST = NeuralNetTrainer.OBSERVER_BURST
 
-    def __init__(self, data_x, data_y, group, raw_u8=False, seed=1):
+    def __init__(self, data_x, data_y, group, raw_u8=False, seed=1, held_out=None):
+        """held_out: (x, y), uploaded as the group's held-out set (NeuralNetTrainer)."""
         self.group = group
         if raw_u8:
             group.upload_dataset_u8(data_x, data_y)
         else:
             group.upload_dataset(data_x, data_y)
+        if held_out is not None:
+            (group.upload_held_out_u8 if raw_u8 else group.upload_held_out)(held_out[0], held_out[1])
         self.size = group._dataset_rows
         if np.ndim(seed) == 0:
             self.sampler = Sampler(self.size, seed)
@@ -196,10 +209,16 @@ def read_idx_labels(path):
     return data
 
 
-def accuracy(net, labels=None, first=0, n=None):
+def accuracy(net, labels=None, first=0, n=None, held_out=False):
     """testOnTrainingData / testOnTestData (MT:159-197) over dataset rows [first, first+len):
     hit when the `>=` argmax of propagate() equals the label.  With labels = None the expected classes are the dataset's own
-    expected rows (MT:186-188) and the whole loop runs on the device (gnn_mlp_count_hits_range: one readback)."""
+    expected rows (MT:186-188) and the whole loop runs on the device (gnn_mlp_count_hits_range: one readback).
+    held_out=True: the rows of the net's held-out set against their own expected rows (testOnTestData, MT:159-172)."""
+    if held_out:
+        if labels is not None:
+            raise ValueError("held_out=True counts against the held-out set's own expected rows")
+        n = net.held_out_size - first if n is None else n
+        return net.count_hits_range(first, n, held_out=True) / n
     if labels is None:
         n = net.dataset_size - first if n is None else n
         return net.count_hits_range(first, n) / n

@@ -217,6 +217,50 @@ int gnn_mlp_train_sampled(gnn_mlp_t *h, gnn_sampler_t *s, int iterations, int ba
 int gnn_mlp_train_sampled_observed(gnn_mlp_t *h, gnn_sampler_t *s, int iterations, int batch, double step,
                                    double momentum, int noise, int validation_size, double *val_loss);
 
+/* ---- the held-out set (MNISTTrainer's test rows, MT:98, MT:159-172) ------------------------------
+ * A second resident data set beside the training set: the same layout and encodings (gnn_mlp_upload_dataset / _u8), read by
+ * the evaluation passes only.  An upload replaces the previous held-out set after a stream synchronisation; it touches neither
+ * the training set nor the look-ahead state (no training row is renamed) nor a pending host-batch update's result, and
+ * uploading the training set leaves the held-out set alone.  On a member of a group -> GNN_ERR_STATE (the group holds ONE
+ * copy: gnn_mlp_group_upload_held_out).  Freed with its owner. */
+typedef enum { GNN_SET_TRAIN = 0, GNN_SET_HELD_OUT = 1 } gnn_data_set;
+int gnn_mlp_upload_held_out(gnn_mlp_t *h, const double *X, const double *Y, int64_t N);
+int gnn_mlp_upload_held_out_u8(gnn_mlp_t *h, const uint8_t *pixels, const uint8_t *labels, int64_t N);
+/* rows of the named set: 0 when nothing was uploaded, -1 for a null handle or a `set` that is neither value */
+int64_t gnn_mlp_set_rows(const gnn_mlp_t *h, int set);
+/* gnn_mlp_evaluate_range with the set named: testOnTrainingData (MT:180-197) with GNN_SET_TRAIN -- bit for bit
+ * gnn_mlp_evaluate_range --, testOnTestData (MT:159-172) with GNN_SET_HELD_OUT -- bit for bit what gnn_mlp_evaluate_range
+ * returns on a handle with the same weights whose training set is those rows.  The same launches, block sizes and summing
+ * order; one readback; writes no weight, momentum, step count or look-ahead state.  The named set never uploaded ->
+ * GNN_ERR_STATE; rows outside it, or a `set` that is neither value -> GNN_ERR_BAD_ARG.  The two accuracies are one row of
+ * logs/trainLog.csv (MT:241). */
+int gnn_mlp_evaluate_set_range(gnn_mlp_t *h, int set, int64_t first, int64_t n, int64_t *hits, double *loss_sum,
+                               int64_t *confusion /* [d_out][d_out] */, int32_t *labels /* [n] */);
+
+/* A training loop with a held-out curve that keeps the best weights ON THE DEVICE (csrc/keep_best_kernel.h).  Trains exactly
+ * as gnn_mlp_train_sampled: weights, momentum, `time` and the sampler end bit for bit where that call leaves them.  Point p in
+ * [0, P), P = gnn_mlp_held_out_points(iterations, every) = ceil(iterations / every), is taken after iteration
+ * min((p + 1) * every, iterations), counted from 1: rows [0, held_rows) of the held-out set are evaluated on the device,
+ * point_hits[p] and point_loss[p] (the SUM, like loss_sum) bit for bit what gnn_mlp_evaluate_set_range(h, GNN_SET_HELD_OUT, 0,
+ * held_rows, ..) would return at that moment (testOnTestData, MT:159-172, along the run).  The running best is decided in point
+ * order, starting from "none".  Point p becomes the best when
+ *   GNN_BEST_LOSS: its loss is not NaN and (there is no best yet, or its loss is strictly lower);
+ *   GNN_BEST_HITS: there is no best yet, or it has strictly more hits, or equal hits and a strictly lower loss (a NaN loss is
+ *                  never lower).
+ * Ties keep the earlier point.  *best_point = the final best, -1 when GNN_BEST_LOSS never saw a number.  best_weights, when not
+ * null, receives the weights the net held AT that point, in the layout of gnn_mlp_get_weights and bit for bit what that call
+ * would have returned there; left unwritten when *best_point is -1.  A point is one launch behind its evaluation launches and
+ * writes nothing the step reads: the chain of two-launch steps runs on behind it; curves, *best_point and the weights come back
+ * behind ONE synchronisation.  Refused before any step and any draw: every < 1, held_rows outside [1, held-out rows], a null
+ * point_hits / point_loss / best_point, a `rule` that is neither value -> GNN_ERR_BAD_ARG; no held-out set -> GNN_ERR_STATE;
+ * noise != 0 -> GNN_ERR_UNSUPPORTED; everything gnn_mlp_train_sampled refuses, with its codes. */
+typedef enum { GNN_BEST_LOSS = 0, GNN_BEST_HITS = 1 } gnn_best_rule;
+int gnn_mlp_held_out_points(int iterations, int every); /* P; -1 unless iterations >= 1 and every >= 1 */
+int gnn_mlp_train_sampled_held_out(gnn_mlp_t *h, gnn_sampler_t *s, int iterations, int batch, double step, double momentum,
+                                   int noise, int every, int64_t held_rows, int rule,
+                                   int64_t *point_hits /* [P] */, double *point_loss /* [P] */,
+                                   int32_t *best_point, double *best_weights /* [num_params] or null */);
+
 /* ---- data-parallel hooks (one process per GPU; the exchange is the caller's collective) -- */
 
 /* The reference sums per-sample gradients at SCE:305-322 and divides by batch.size() at
@@ -420,6 +464,32 @@ int gnn_mlp_group_input_gradient_range(gnn_mlp_group_t *g, int64_t first, int64_
                                        double *member_saliency /* [K][d_out][d_0] or null */,
                                        double *ensemble_saliency /* [d_out][d_0] or null */,
                                        int64_t *class_rows /* [d_out] or null */);
+/* The group's held-out set (gnn_mlp_upload_held_out*): ONE copy, which the members see through their borrowed handles; the
+ * rules of the lone uploads hold for every member. */
+int gnn_mlp_group_upload_held_out(gnn_mlp_group_t *g, const double *X, const double *Y, int64_t N);
+int gnn_mlp_group_upload_held_out_u8(gnn_mlp_group_t *g, const uint8_t *pixels, const uint8_t *labels, int64_t N);
+/* gnn_mlp_group_evaluate_range, _ensemble_range and _confusion_range with the set named (gnn_data_set; MT:159-172 on
+ * GNN_SET_HELD_OUT): bit for bit the existing call with GNN_SET_TRAIN, and with GNN_SET_HELD_OUT what it returns on a group with
+ * the same weights whose training set is those rows.  The named set never uploaded -> GNN_ERR_STATE; rows outside it, or a
+ * `set` that is neither value -> GNN_ERR_BAD_ARG. */
+int gnn_mlp_group_evaluate_set_range(gnn_mlp_group_t *g, int set, int64_t first, int64_t n, int64_t *member_hits,
+                                     double *member_loss_sum, int64_t *ensemble_hits);
+int gnn_mlp_group_ensemble_set_range(gnn_mlp_group_t *g, int set, int64_t first, int64_t n, double *mean_out, int32_t *labels);
+int gnn_mlp_group_confusion_set_range(gnn_mlp_group_t *g, int set, int64_t first, int64_t n, int64_t *member_confusion,
+                                      int64_t *ensemble_confusion, int32_t *member_labels);
+/* gnn_mlp_train_sampled_held_out for every member: trains exactly as gnn_mlp_group_train_sampled_sizes (one sampler and one
+ * batch size per member; groups without grouped launches member after member), and at point p column k of point_hits /
+ * point_loss ([p * K + k]) and ensemble_hits[p] are bit for bit what gnn_mlp_group_evaluate_set_range(g, GNN_SET_HELD_OUT, 0,
+ * held_rows, ..) would return there (MT:159-172 for every member, and the row of MT:241 along the run).  The best point is
+ * decided per member; best_weights[k * num_params ..] are member k's weights at best_point[k] (unwritten when that is -1).
+ * One keep_best launch per point serves all members.  Refuses what the lone call and gnn_mlp_group_train_sampled_sizes
+ * refuse, with their codes. */
+int gnn_mlp_group_train_sampled_held_out(gnn_mlp_group_t *g, gnn_sampler_t *const *samplers, int iterations,
+                                         const int32_t *batches, const double *steps, const double *momenta, int noise,
+                                         int every, int64_t held_rows, int rule,
+                                         int64_t *point_hits /* [P][K] */, double *point_loss /* [P][K] */,
+                                         int64_t *ensemble_hits /* [P] or null */,
+                                         int32_t *best_point /* [K] */, double *best_weights /* [K][num_params] or null */);
 
 /* ---- shape specialisation ---------------------------------------------------------------------
  * The per-row-block kernel of the fused small-net path is a template over the net's shape; with
