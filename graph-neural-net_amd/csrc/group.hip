@@ -10,6 +10,12 @@
 // outside the arena, a second relocatable range; a call with one BATCH SIZE per member, gnn_mlp_group_train_sampled_sizes, hands
 // the grouped launches every member's own row count: the end of this file.)  Nets off the two-launch path are stepped one member
 // after another through their own handles: the same results, no speed-up.
+//
+// Every training entry point that launches for the group does so through ONE scaffold, GroupedCall::run, the only place that
+// spells enter_grouped / GroupScope / leave_grouped.  Its rules: leave_grouped also runs when the loop failed (the steps it did
+// take are the members' too); everything a call allocates is allocated before enter_grouped; the counters of a call with one
+// sampler per member are zeroed before the decision to go member after member; and the GroupScope ends before the members'
+// state is copied.  An entry point adds its checks, its observer and its fallback, nothing of the above.
 #include "handle.h"
 
 #include <algorithm>
@@ -83,6 +89,84 @@ int check_per_member(const gnn_mlp_group *g, const double *steps, const double *
     if (!steps || !momenta) return fail(GNN_ERR_BAD_ARG, "steps and momenta: one value per member, not null");
     for (int k = 0; k < g->K; k++)
         if (!(steps[k] > 0)) return fail(GNN_ERR_BAD_ARG, "step must be positive (SCE:301)");
+    return GNN_OK;
+}
+
+// One call's grouped launches (the head of this file): run() hands `loop` the GroupLaunch under which member 0 launches for the
+// group, and whatever status the loop returns -- the steps it took are taken -- moves member 0's step count and look-ahead
+// state to the members.  The GroupLaunch lives in run() alone, so what points into it (EachMember, SizedMembers below) can only
+// be made inside the loop and is gone before it; what such an object has to say to leave_grouped it writes to `mixed` / `track`.
+struct GroupedCall {
+    gnn_mlp_group *g;
+    bool sized = false;   // one batch size per member: the launches take every member's row count, the members leave with `track`
+    bool counted = false; // one sampler per member: g->each_grouped / each_mixed say how the iterations were stepped
+    int64_t mixed = 0;    // iterations the loop stepped member after member, through the members' own handles: step counts included
+    GroupSizes track;     // sized: member k's sizes of the batches member 0's state names (valid once enter_grouped has run)
+
+    template <class Loop> int run(const double *steps, const double *momenta, Loop &&loop) {
+        TRY(enter_grouped(g));
+        GroupLaunch gl;
+        TRY(group_launch(g, steps, momenta, &gl));
+        gl.sized = sized;
+        gnn_mlp *h0 = g->m[0];
+        const int t0 = h0->time;
+        int rc;
+        {
+            GroupScope scope(h0, &gl);
+            rc = loop(gl);
+        }
+        const int done = h0->time - t0;
+        // (a mixed iteration advanced every member's step count through its own handle: only the grouped ones are member 0's alone)
+        leave_grouped(g, done - (int)mixed, nullptr, 0, sized ? &track : nullptr);
+        if (counted) { g->each_mixed = mixed; g->each_grouped = done - mixed; }
+        return rc;
+    }
+};
+
+// Member k trained through its own handle, as the lone net it is.  With a curve (val_loss, [iterations][K]): column k is the lone
+// handle's curve.
+int member_sampled(gnn_mlp_group *g, int k, gnn_sampler_t *s, int iterations, int batch, double step, double momentum, int noise,
+                   int validation_size, double *val_loss) {
+    const int K = g->K;
+    gnn_mlp *h = g->m[(size_t)k];
+    if (!val_loss) return gnn_mlp_train_sampled(h, s, iterations, batch, step, momentum, noise);
+    std::vector<double> col((size_t)iterations);
+    TRY(gnn_mlp_train_sampled_observed(h, s, iterations, batch, step, momentum, noise, validation_size, col.data()));
+    for (int i = 0; i < iterations; i++) val_loss[(size_t)i * K + k] = col[(size_t)i];
+    return GNN_OK;
+}
+// The two ways member after member.  ONE sampler: every member draws what the sampler draws from its state at the call -- it is
+// rewound for each and ends where the last member's run leaves it ...
+int members_one_sampler(gnn_mlp_group *g, gnn_sampler_t *s, int iterations, int batch, const double *steps, const double *momenta,
+                        int noise, int validation_size = 0, double *val_loss = nullptr) {
+    std::unique_ptr<gnn_sampler_t, int (*)(gnn_sampler_t *)> start(sampler_copy(s), gnn_sampler_destroy);
+    for (int k = 0; k < g->K; k++) {
+        if (k) sampler_assign(s, start.get());
+        TRY(member_sampled(g, k, s, iterations, batch, steps[k], momenta[k], noise, validation_size, val_loss));
+    }
+    return GNN_OK;
+}
+// ... a sampler per member: each with its own sampler and batch size, never rewound.
+int members_own_samplers(gnn_mlp_group *g, gnn_sampler_t *const *samplers, int iterations, const int *batches, const double *steps,
+                         const double *momenta, int noise, int validation_size = 0, double *val_loss = nullptr) {
+    for (int k = 0; k < g->K; k++)
+        TRY(member_sampled(g, k, samplers[k], iterations, batches[k], steps[k], momenta[k], noise, validation_size, val_loss));
+    return GNN_OK;
+}
+
+// What a call with one sampler per member refuses about them, member k against its own sampler and batch size; `val_loss`: the
+// curve request.  (The callers that take an ARRAY of batch sizes refuse a null one themselves, between "samplers is null" and the
+// samplers' own checks: `samplers && !batches` in front of this.)
+int check_member_samplers(gnn_mlp_group *g, gnn_sampler_t *const *samplers, int iterations, const int *batches, const double *steps,
+                          int noise, int validation_size, const double *val_loss) {
+    const int K = g->K;
+    if (!samplers) return fail(GNN_ERR_BAD_ARG, "samplers is null");
+    for (int k = 0; k < K; k++) if (!samplers[k]) return fail(GNN_ERR_BAD_ARG, "null sampler");
+    for (int k = 0; k < K; k++)
+        for (int j = 0; j < k; j++)
+            if (samplers[j] == samplers[k]) return fail(GNN_ERR_BAD_ARG, "the same sampler for two members: every member draws from its own");
+    for (int k = 0; k < K; k++) TRY(train_sampled_checks(g->m[k], samplers[k], iterations, batches[k], steps[k], noise));
+    if (val_loss && (validation_size <= 0 || validation_size > g->m[0]->dataset_n)) return fail(GNN_ERR_BAD_ARG, "validation size outside the dataset (NNT:104)");
     return GNN_OK;
 }
 
@@ -226,17 +310,7 @@ int gnn_mlp_group_train_range(gnn_mlp_group_t *g, int64_t first, int B, int n_st
         for (int k = 0; k < g->K; k++) TRY(gnn_mlp_train_range(g->m[(size_t)k], first, B, n_steps, steps[k], momenta[k]));
         return GNN_OK;
     }
-    TRY(enter_grouped(g));
-    GroupLaunch gl;
-    TRY(group_launch(g, steps, momenta, &gl));
-    const int t0 = h0->time;
-    int rc;
-    {
-        GroupScope scope(h0, &gl);
-        rc = train_range_steps(h0, first, B, 0, n_steps, steps[0], momenta[0]);
-    }
-    leave_grouped(g, h0->time - t0);
-    return rc;
+    return GroupedCall{g}.run(steps, momenta, [&](GroupLaunch &) { return train_range_steps(h0, first, B, 0, n_steps, steps[0], momenta[0]); });
 }); }
 
 int gnn_mlp_group_train_sampled(gnn_mlp_group_t *g, gnn_sampler_t *s, int iterations, int batch, const double *steps,
@@ -245,25 +319,8 @@ int gnn_mlp_group_train_sampled(gnn_mlp_group_t *g, gnn_sampler_t *s, int iterat
     TRY(check_per_member(g, steps, momenta));
     gnn_mlp *h0 = g->m[0];
     TRY(train_sampled_checks(h0, s, iterations, batch, steps[0], noise));
-    if (g->K == 1 || !g->grouped) { // every member draws what the sampler draws from its state at the call
-        std::unique_ptr<gnn_sampler_t, int (*)(gnn_sampler_t *)> start(sampler_copy(s), gnn_sampler_destroy);
-        for (int k = 0; k < g->K; k++) {
-            if (k) sampler_assign(s, start.get());
-            TRY(gnn_mlp_train_sampled(g->m[(size_t)k], s, iterations, batch, steps[k], momenta[k], noise));
-        }
-        return GNN_OK;
-    }
-    TRY(enter_grouped(g));
-    GroupLaunch gl;
-    TRY(group_launch(g, steps, momenta, &gl));
-    const int t0 = h0->time;
-    int rc;
-    {
-        GroupScope scope(h0, &gl);
-        rc = train_sampled_run(h0, s, iterations, batch, steps[0], momenta[0], noise);
-    }
-    leave_grouped(g, h0->time - t0);
-    return rc;
+    if (g->K == 1 || !g->grouped) return members_one_sampler(g, s, iterations, batch, steps, momenta, noise);
+    return GroupedCall{g}.run(steps, momenta, [&](GroupLaunch &) { return train_sampled_run(h0, s, iterations, batch, steps[0], momenta[0], noise); });
 }); }
 
 /* The observed loop (NNT:68-72 / 75-79) of a group: the sampled loops with, behind every step and still under the
@@ -272,10 +329,39 @@ int gnn_mlp_group_train_sampled(gnn_mlp_group_t *g, gnn_sampler_t *s, int iterat
  * into d_val[i][k] whenever it is full and behind the last step.  Everything is allocated and checked before the first step. */
 namespace {
 constexpr int kCurveRows = 256;
-struct GroupValidation : SampledObserver {
-    gnn_mlp_group *g; int validation_size, iterations, M; int64_t stride;
+// What surrounds an observer that leaves the members' validation loss SUMS on the device (this one, MemberValidation below): its
+// buffers, made in front of the first step, and the sums' way to the caller's curve.
+struct CurveObserver : SampledObserver {
+    gnn_mlp_group *g; int validation_size, iterations; int64_t stride;
     float *d_rows; double *d_val;
+    DevScratch rows, val;
+    // n_rows: the vectors of `stride` per-row losses the observer keeps (0: none, d_rows null); d_val: iterations * K sums
+    int make(gnn_mlp_group *g_, int iterations_, int validation_size_, size_t n_rows) {
+        g = g_; validation_size = validation_size_; iterations = iterations_; stride = pad_up(validation_size);
+        if (n_rows) TRY(rows.alloc(sizeof(float) * n_rows * (size_t)stride));
+        TRY(val.alloc(sizeof(double) * (size_t)iterations * g->K));
+        d_rows = rows.as<float>(); d_val = val.as<double>();
+        return GNN_OK;
+    }
+    // (the loop has waited for the stream behind the last sum: one readback)  by_member: the sums lie [k][i], else [i][K]
+    int read(bool by_member, double *val_loss) const {
+        const int K = g->K;
+        std::vector<double> sums((size_t)iterations * K);
+        HIP_TRY(hipMemcpy(sums.data(), val.p, sizeof(double) * sums.size(), hipMemcpyDeviceToHost));
+        for (size_t at = 0; at < sums.size(); at++) { // (at = i * K + k)
+            const size_t i = at / K, k = at % K;
+            val_loss[at] = sums[by_member ? k * iterations + i : at] / (double)validation_size; // NNT:112
+        }
+        return GNN_OK;
+    }
+};
+struct GroupValidation : CurveObserver {
+    int M;
     int summed = 0; // iterations whose rows are summed already (or whose sum is enqueued)
+    int make(gnn_mlp_group *g_, int iterations_, int validation_size_) {
+        M = std::min(iterations_, kCurveRows);
+        return CurveObserver::make(g_, iterations_, validation_size_, (size_t)M * g_->K);
+    }
     int sum_through(int i_end) {
         if (i_end == summed) return GNN_OK;
         TRY(enqueue_group_curve_sum(g, d_rows, i_end - summed, stride, validation_size, d_val + (size_t)summed * g->K)); // (summed is a multiple of M: matrix rows 0 ..)
@@ -303,39 +389,12 @@ int gnn_mlp_group_train_sampled_observed(gnn_mlp_group_t *g, gnn_sampler_t *s, i
     TRY(train_sampled_checks(h0, s, iterations, batch, steps[0], noise));
     if (!val_loss) return fail(GNN_ERR_BAD_ARG, "null output");
     if (validation_size <= 0 || validation_size > h0->dataset_n) return fail(GNN_ERR_BAD_ARG, "validation size outside the dataset (NNT:104)");
-    const int K = g->K;
-    if (gnn_mlp_group_observed_launches(g) != 3) { // member after member, the sampler rewound for each: column k is the lone handle's curve
-        std::unique_ptr<gnn_sampler_t, int (*)(gnn_sampler_t *)> start(sampler_copy(s), gnn_sampler_destroy);
-        std::vector<double> col((size_t)iterations);
-        for (int k = 0; k < K; k++) {
-            if (k) sampler_assign(s, start.get());
-            TRY(gnn_mlp_train_sampled_observed(g->m[(size_t)k], s, iterations, batch, steps[k], momenta[k], noise, validation_size, col.data()));
-            for (int i = 0; i < iterations; i++) val_loss[(size_t)i * K + k] = col[(size_t)i];
-        }
-        return GNN_OK;
-    }
+    if (gnn_mlp_group_observed_launches(g) != 3) // member after member, the sampler rewound for each
+        return members_one_sampler(g, s, iterations, batch, steps, momenta, noise, validation_size, val_loss);
     GroupValidation obs;
-    obs.g = g; obs.validation_size = validation_size; obs.iterations = iterations;
-    obs.M = std::min(iterations, kCurveRows); obs.stride = pad_up(validation_size);
-    DevScratch rows, val;
-    TRY(rows.alloc(sizeof(float) * (size_t)obs.M * K * (size_t)obs.stride));
-    TRY(val.alloc(sizeof(double) * (size_t)iterations * K));
-    obs.d_rows = rows.as<float>(); obs.d_val = val.as<double>();
-    TRY(enter_grouped(g));
-    GroupLaunch gl;
-    TRY(group_launch(g, steps, momenta, &gl));
-    const int t0 = h0->time;
-    int rc;
-    {
-        GroupScope scope(h0, &gl);
-        rc = train_sampled_run(h0, s, iterations, batch, steps[0], momenta[0], noise, &obs);
-    }
-    leave_grouped(g, h0->time - t0);
-    TRY(rc);
-    // (the loop has waited for the stream behind the last sum: one readback)
-    HIP_TRY(hipMemcpy(val_loss, val.p, sizeof(double) * (size_t)iterations * K, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < (size_t)iterations * K; i++) val_loss[i] /= (double)validation_size; // NNT:112
-    return GNN_OK;
+    TRY(obs.make(g, iterations, validation_size));
+    TRY(GroupedCall{g}.run(steps, momenta, [&](GroupLaunch &) { return train_sampled_run(h0, s, iterations, batch, steps[0], momenta[0], noise, &obs); }));
+    return obs.read(false, val_loss);
 }); }
 
 } // extern "C"
@@ -350,7 +409,9 @@ namespace {
 struct EachMember : SampledEach {
     gnn_mlp_group *g; GroupLaunch *gl; const double *steps, *momenta;
     size_t slice_elems = 0;
-    int64_t mixed = 0;
+    int64_t &mixed; // (the call's: GroupedCall::run hands the members the grouped iterations only)
+    EachMember(GroupedCall &call, GroupLaunch &gl_, const double *steps_, const double *momenta_)
+        : g(call.g), gl(&gl_), steps(steps_), momenta(momenta_), mixed(call.mixed) {}
     ~EachMember() override { if (gl->idx_lo) region(nullptr, 0); } // (the loop was left by an exception)
     void region(const int32_t *lo, size_t slice_bytes) override {
         if (!lo) { // about to be released: no member keeps an address inside it
@@ -378,70 +439,6 @@ struct EachMember : SampledEach {
 };
 } // namespace
 
-extern "C" {
-
-int gnn_mlp_group_train_sampled_each(gnn_mlp_group_t *g, gnn_sampler_t *const *samplers, int iterations, int batch,
-                                     const double *steps, const double *momenta, int noise, int validation_size,
-                                     double *val_loss) { return guarded([&]() -> int {
-    TRY(check_group(g));
-    TRY(check_per_member(g, steps, momenta));
-    const int K = g->K;
-    gnn_mlp *h0 = g->m[0];
-    if (!samplers) return fail(GNN_ERR_BAD_ARG, "samplers is null");
-    for (int k = 0; k < K; k++) if (!samplers[k]) return fail(GNN_ERR_BAD_ARG, "null sampler");
-    for (int k = 0; k < K; k++)
-        for (int j = 0; j < k; j++)
-            if (samplers[j] == samplers[k]) return fail(GNN_ERR_BAD_ARG, "the same sampler for two members: every member draws from its own");
-    for (int k = 0; k < K; k++) TRY(train_sampled_checks(g->m[k], samplers[k], iterations, batch, steps[k], noise));
-    if (val_loss && (validation_size <= 0 || validation_size > h0->dataset_n)) return fail(GNN_ERR_BAD_ARG, "validation size outside the dataset (NNT:104)");
-    g->each_grouped = g->each_mixed = 0;
-    const bool fallback = K == 1 || !g->grouped || (val_loss && gnn_mlp_group_observed_launches(g) != 3);
-    if (fallback) { // member after member, each with its own sampler through its own handle
-        std::vector<double> col(val_loss ? (size_t)iterations : 0);
-        for (int k = 0; k < K; k++) {
-            if (!val_loss) { TRY(gnn_mlp_train_sampled(g->m[(size_t)k], samplers[k], iterations, batch, steps[k], momenta[k], noise)); continue; }
-            TRY(gnn_mlp_train_sampled_observed(g->m[(size_t)k], samplers[k], iterations, batch, steps[k], momenta[k], noise, validation_size, col.data()));
-            for (int i = 0; i < iterations; i++) val_loss[(size_t)i * K + k] = col[(size_t)i];
-        }
-        g->each_mixed = iterations;
-        return GNN_OK;
-    }
-    GroupValidation obs;
-    DevScratch rows, val;
-    if (val_loss) {
-        obs.g = g; obs.validation_size = validation_size; obs.iterations = iterations;
-        obs.M = std::min(iterations, kCurveRows); obs.stride = pad_up(validation_size);
-        TRY(rows.alloc(sizeof(float) * (size_t)obs.M * K * (size_t)obs.stride));
-        TRY(val.alloc(sizeof(double) * (size_t)iterations * K));
-        obs.d_rows = rows.as<float>(); obs.d_val = val.as<double>();
-    }
-    TRY(enter_grouped(g));
-    GroupLaunch gl;
-    TRY(group_launch(g, steps, momenta, &gl));
-    EachMember each;
-    each.g = g; each.gl = &gl; each.steps = steps; each.momenta = momenta;
-    int nominal[GROUP_MAX];
-    for (int k = 0; k < K; k++) nominal[k] = batch;
-    const int t0 = h0->time;
-    int rc;
-    {
-        GroupScope scope(h0, &gl);
-        rc = train_sampled_run_each(h0, samplers, K, iterations, nominal, steps[0], momenta[0], noise, val_loss ? &obs : nullptr, &each);
-    }
-    const int done = h0->time - t0;
-    // (a mixed iteration advanced every member's step count through its own handle: only the grouped ones are member 0's alone)
-    leave_grouped(g, done - (int)each.mixed);
-    g->each_mixed = each.mixed; g->each_grouped = done - each.mixed;
-    TRY(rc);
-    if (val_loss) {
-        HIP_TRY(hipMemcpy(val_loss, val.p, sizeof(double) * (size_t)iterations * K, hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < (size_t)iterations * K; i++) val_loss[i] /= (double)validation_size; // NNT:112
-    }
-    return GNN_OK;
-}); }
-
-} // extern "C"
-
 /* One batch size per member (the reference's recorded sweep, logs/trainLog.csv rows 1-3: three step sizes AND three batch sizes).
  * The loop is the one above with ring m drawn at batches[m]; EVERY iteration is the two grouped launches, member k with its own
  * live row count now and in the announced iteration (GroupLaunch::rows / next_rows, group_kernels.h) -- a refill that shortens
@@ -449,7 +446,8 @@ int gnn_mlp_group_train_sampled_each(gnn_mlp_group_t *g, gnn_sampler_t *const *s
 namespace {
 struct SizedMembers : SampledEach {
     gnn_mlp_group *g; GroupLaunch *gl;
-    GroupSizes track; // member k's sizes of the batches member 0's state names, step by step
+    GroupSizes &track; // member k's sizes of the batches member 0's state names, step by step (the call's: the members leave with them)
+    SizedMembers(GroupedCall &call, GroupLaunch &gl_) : g(call.g), gl(&gl_), track(call.track) { track = g->sizes; }
     ~SizedMembers() override { if (gl->idx_lo) region(nullptr, 0); } // (the loop was left by an exception)
     void region(const int32_t *lo, size_t slice_bytes) override {
         if (!lo) { // about to be released: no member keeps an address inside it
@@ -474,9 +472,12 @@ struct SizedMembers : SampledEach {
 // kernels read the weights the step has just written and touch neither slabs nor staged rows.  Sums to val[k][i]: the per-row
 // losses kept in rows[k][i][..] and summed by one launch behind the loop when that fits 1 GiB, else summed per iteration (the
 // same fp64 sum either way: eval_kernels.h).
-struct MemberValidation : SampledObserver {
-    gnn_mlp_group *g; int validation_size, iterations; int64_t stride;
-    float *d_rows; double *d_val;
+struct MemberValidation : CurveObserver {
+    int make(gnn_mlp_group *g_, int iterations_, int validation_size_) {
+        const int K = g_->K;
+        const bool rows_form = eval_block_rows(g_->m[0], validation_size_) >= validation_size_ && (int64_t)K * iterations_ * pad_up(validation_size_) * 4 <= (1ll << 30);
+        return CurveObserver::make(g_, iterations_, validation_size_, rows_form ? (size_t)K * (size_t)iterations_ : 0);
+    }
     int after_step(int i) override {
         for (int k = 0; k < g->K; k++) {
             gnn_mlp *h = g->m[(size_t)k];
@@ -492,79 +493,61 @@ struct MemberValidation : SampledObserver {
         return GNN_OK;
     }
 };
-} // namespace
 
-extern "C" {
-
-int gnn_mlp_group_train_sampled_sizes(gnn_mlp_group_t *g, gnn_sampler_t *const *samplers, int iterations, const int32_t *batches,
-                                      const double *steps, const double *momenta, int noise, int validation_size,
-                                      double *val_loss) { return guarded([&]() -> int {
+// gnn_mlp_group_train_sampled_each (`sized` false: batches[] holds the one size K times) and gnn_mlp_group_train_sampled_sizes:
+// one call, but for who stands on the group's side of the loop (EachMember / SizedMembers), who observes it (GroupValidation:
+// sums [i][K] every kCurveRows iterations / MemberValidation: sums [k][i]) and what GroupedCall makes of a mixed iteration.
+int train_sampled_members(gnn_mlp_group *g, gnn_sampler_t *const *samplers, int iterations, const int *batches, const double *steps,
+                          const double *momenta, int noise, int validation_size, double *val_loss, bool sized) {
     TRY(check_group(g));
     TRY(check_per_member(g, steps, momenta));
     const int K = g->K;
     gnn_mlp *h0 = g->m[0];
-    if (!samplers) return fail(GNN_ERR_BAD_ARG, "samplers is null");
-    if (!batches) return fail(GNN_ERR_BAD_ARG, "batches is null: one batch size per member");
-    for (int k = 0; k < K; k++) if (!samplers[k]) return fail(GNN_ERR_BAD_ARG, "null sampler");
-    for (int k = 0; k < K; k++)
-        for (int j = 0; j < k; j++)
-            if (samplers[j] == samplers[k]) return fail(GNN_ERR_BAD_ARG, "the same sampler for two members: every member draws from its own");
-    for (int k = 0; k < K; k++) TRY(train_sampled_checks(g->m[k], samplers[k], iterations, batches[k], steps[k], noise));
-    if (val_loss && (validation_size <= 0 || validation_size > h0->dataset_n)) return fail(GNN_ERR_BAD_ARG, "validation size outside the dataset (NNT:104)");
+    if (samplers && !batches) return fail(GNN_ERR_BAD_ARG, "batches is null: one batch size per member"); // (_sizes: _each has its own array)
+    TRY(check_member_samplers(g, samplers, iterations, batches, steps, noise, validation_size, val_loss));
     g->each_grouped = g->each_mixed = 0;
-    const bool fallback = K == 1 || !g->grouped || (val_loss && gnn_mlp_group_observed_launches(g) != 3);
-    if (fallback) { // member after member, each with its own sampler and batch size through its own handle
-        std::vector<double> col(val_loss ? (size_t)iterations : 0);
-        for (int k = 0; k < K; k++) {
-            if (!val_loss) { TRY(gnn_mlp_train_sampled(g->m[(size_t)k], samplers[k], iterations, batches[k], steps[k], momenta[k], noise)); continue; }
-            TRY(gnn_mlp_train_sampled_observed(g->m[(size_t)k], samplers[k], iterations, batches[k], steps[k], momenta[k], noise, validation_size, col.data()));
-            for (int i = 0; i < iterations; i++) val_loss[(size_t)i * K + k] = col[(size_t)i];
-        }
+    if (K == 1 || !g->grouped || (val_loss && gnn_mlp_group_observed_launches(g) != 3)) { // member after member
+        TRY(members_own_samplers(g, samplers, iterations, batches, steps, momenta, noise, validation_size, val_loss));
         g->each_mixed = iterations;
         return GNN_OK;
     }
-    MemberValidation obs;
-    DevScratch rows, val;
-    bool rows_form = false;
-    if (val_loss) {
-        obs.g = g; obs.validation_size = validation_size; obs.iterations = iterations; obs.stride = pad_up(validation_size);
-        rows_form = eval_block_rows(h0, validation_size) >= validation_size && (int64_t)K * iterations * obs.stride * 4 <= (1ll << 30);
-        if (rows_form) TRY(rows.alloc(sizeof(float) * (size_t)K * (size_t)iterations * (size_t)obs.stride));
-        TRY(val.alloc(sizeof(double) * (size_t)iterations * K));
-        obs.d_rows = rows_form ? rows.as<float>() : nullptr; obs.d_val = val.as<double>();
+    GroupValidation together;
+    MemberValidation alone;
+    CurveObserver *obs = nullptr;
+    if (val_loss && !sized) { TRY(together.make(g, iterations, validation_size)); obs = &together; }
+    if (val_loss && sized) { TRY(alone.make(g, iterations, validation_size)); obs = &alone; }
+    GroupedCall call{g, sized, /* counted */ true};
+    TRY(call.run(steps, momenta, [&](GroupLaunch &gl) {
+        auto loop = [&](SampledEach *each) { return train_sampled_run_each(h0, samplers, K, iterations, batches, steps[0], momenta[0], noise, obs, each); };
+        if (sized) { SizedMembers each(call, gl); return loop(&each); }
+        EachMember each(call, gl, steps, momenta);
+        return loop(&each);
+    }));
+    if (!val_loss) return GNN_OK;
+    if (sized && alone.d_rows) { // the per-row losses were kept: their sums in one launch
+        hipLaunchKernelGGL(sum_rows_kernel, dim3((unsigned)K * (unsigned)iterations), dim3(256), 0, h0->stream,
+                           RowSumParams{alone.d_rows, alone.stride, validation_size, alone.d_val});
+        TRY_LAUNCHES(h0);
+        HIP_TRY(hipStreamSynchronize(h0->stream));
     }
-    TRY(enter_grouped(g));
-    GroupLaunch gl;
-    TRY(group_launch(g, steps, momenta, &gl));
-    gl.sized = true;
-    SizedMembers each;
-    each.g = g; each.gl = &gl; each.track = g->sizes;
-    int nominal[GROUP_MAX];
-    for (int k = 0; k < K; k++) nominal[k] = batches[k];
-    const int t0 = h0->time;
-    int rc;
-    {
-        GroupScope scope(h0, &gl);
-        rc = train_sampled_run_each(h0, samplers, K, iterations, nominal, steps[0], momenta[0], noise, val_loss ? &obs : nullptr, &each);
-    }
-    const int done = h0->time - t0;
-    leave_grouped(g, done, nullptr, 0, &each.track);
-    g->each_grouped = done;
-    TRY(rc);
-    if (val_loss) {
-        if (rows_form) {
-            hipLaunchKernelGGL(sum_rows_kernel, dim3((unsigned)K * (unsigned)iterations), dim3(256), 0, h0->stream,
-                               RowSumParams{rows.as<float>(), obs.stride, validation_size, val.as<double>()});
-            TRY_LAUNCHES(h0);
-            HIP_TRY(hipStreamSynchronize(h0->stream));
-        }
-        // (the loop has waited for the stream: one readback of val[k][i], transposed on the host)
-        std::vector<double> col((size_t)iterations * K);
-        HIP_TRY(hipMemcpy(col.data(), val.p, sizeof(double) * col.size(), hipMemcpyDeviceToHost));
-        for (int k = 0; k < K; k++)
-            for (int i = 0; i < iterations; i++) val_loss[(size_t)i * K + k] = col[(size_t)k * iterations + i] / (double)validation_size; // NNT:112
-    }
-    return GNN_OK;
+    return obs->read(sized, val_loss); // (val[k][i] of a sized call: transposed on the host)
+}
+} // namespace
+
+extern "C" {
+
+int gnn_mlp_group_train_sampled_each(gnn_mlp_group_t *g, gnn_sampler_t *const *samplers, int iterations, int batch,
+                                     const double *steps, const double *momenta, int noise, int validation_size,
+                                     double *val_loss) { return guarded([&]() -> int {
+    int batches[GROUP_MAX];
+    std::fill(batches, batches + GROUP_MAX, batch);
+    return train_sampled_members(g, samplers, iterations, batches, steps, momenta, noise, validation_size, val_loss, false);
+}); }
+
+int gnn_mlp_group_train_sampled_sizes(gnn_mlp_group_t *g, gnn_sampler_t *const *samplers, int iterations, const int32_t *batches,
+                                      const double *steps, const double *momenta, int noise, int validation_size,
+                                      double *val_loss) { return guarded([&]() -> int {
+    return train_sampled_members(g, samplers, iterations, batches, steps, momenta, noise, validation_size, val_loss, true);
 }); }
 
 } // extern "C"
@@ -618,13 +601,8 @@ int gnn_mlp_group_train_sampled_held_out(gnn_mlp_group_t *g, gnn_sampler_t *cons
     TRY(check_per_member(g, steps, momenta));
     const int K = g->K;
     gnn_mlp *h0 = g->m[0];
-    if (!samplers) return fail(GNN_ERR_BAD_ARG, "samplers is null");
-    if (!batches) return fail(GNN_ERR_BAD_ARG, "batches is null: one batch size per member");
-    for (int k = 0; k < K; k++) if (!samplers[k]) return fail(GNN_ERR_BAD_ARG, "null sampler");
-    for (int k = 0; k < K; k++)
-        for (int j = 0; j < k; j++)
-            if (samplers[j] == samplers[k]) return fail(GNN_ERR_BAD_ARG, "the same sampler for two members: every member draws from its own");
-    for (int k = 0; k < K; k++) TRY(train_sampled_checks(g->m[k], samplers[k], iterations, batches[k], steps[k], noise));
+    if (samplers && !batches) return fail(GNN_ERR_BAD_ARG, "batches is null: one batch size per member");
+    TRY(check_member_samplers(g, samplers, iterations, batches, steps, noise, 0, nullptr));
     TRY(check_held_out_args(h0, every, held_rows, rule, point_hits, point_loss, best_point));
     for (gnn_mlp *h : g->m) TRY(check_handle(h)); // (a member's deferred host-batch update is applied first)
     const int P = gnn_mlp_held_out_points(iterations, every);
@@ -652,7 +630,7 @@ int gnn_mlp_group_train_sampled_held_out(gnn_mlp_group_t *g, gnn_sampler_t *cons
     if (K == 1 || !g->grouped) { // interval by interval, member after member, each with its own sampler and batch size through its own handle
         for (int p = 0; p < P; p++) {
             const int n_it = std::min(every, iterations - p * every);
-            for (int k = 0; k < K; k++) TRY(gnn_mlp_train_sampled(g->m[(size_t)k], samplers[k], n_it, batches[k], steps[k], momenta[k], noise));
+            TRY(members_own_samplers(g, samplers, n_it, batches, steps, momenta, noise));
             TRY(obs.point(p));
         }
         for (gnn_mlp *h : g->m) TRY_LAUNCHES(h);
@@ -660,24 +638,11 @@ int gnn_mlp_group_train_sampled_held_out(gnn_mlp_group_t *g, gnn_sampler_t *cons
         HIP_TRY(hipStreamSynchronize(h0->stream));
         g->each_mixed = iterations;
     } else {
-        TRY(enter_grouped(g));
-        GroupLaunch gl;
-        TRY(group_launch(g, steps, momenta, &gl));
-        gl.sized = true;
-        SizedMembers each;
-        each.g = g; each.gl = &gl; each.track = g->sizes;
-        int nominal[GROUP_MAX];
-        for (int k = 0; k < K; k++) nominal[k] = batches[k];
-        const int t0 = h0->time;
-        int rc;
-        {
-            GroupScope scope(h0, &gl);
-            rc = train_sampled_run_each(h0, samplers, K, iterations, nominal, steps[0], momenta[0], noise, &obs, &each);
-        }
-        const int done = h0->time - t0;
-        leave_grouped(g, done, nullptr, 0, &each.track);
-        g->each_grouped = done;
-        TRY(rc);
+        GroupedCall call{g, /* sized */ true, /* counted */ true};
+        TRY(call.run(steps, momenta, [&](GroupLaunch &gl) {
+            SizedMembers each(call, gl);
+            return train_sampled_run_each(h0, samplers, K, iterations, batches, steps[0], momenta[0], noise, &obs, &each);
+        }));
         // (the loop has waited for the stream behind the readbacks: the ONE synchronisation)
     }
     static_assert(sizeof(unsigned long long) == sizeof(double), "one buffer for counters and sums");
