@@ -34,6 +34,7 @@ void read_env(gnn_mlp *h) {
     h->env_bf16_group_off = is("GNN_MLP_BF16_GROUP", "0");
     h->env_rb_off = is("GNN_MLP_ROWBLOCK", "0");
     h->env_tile_head_off = is("GNN_MLP_TILE_HEAD", "0");
+    h->env_tile_merge_off = is("GNN_MLP_TILE_MERGE", "0");
     h->env_defer_off = is("GNN_MLP_DEFER", "0");
     const char *fg = getenv("GNN_MLP_FIRST_GEMM_ROWS"); // development: from how many rows on the first layer runs as a tiled GEMM (0 = never)
     if (fg) h->first_gemm_rows = atoi(fg);
@@ -871,6 +872,7 @@ int gnn_mlp_specialize(gnn_mlp_t *h) { return guarded([&]() -> int {
 }); }
 int gnn_mlp_specialization(const gnn_mlp_t *h) { return h ? h->specialization : -1; }
 int gnn_mlp_step_launches(const gnn_mlp_t *h) { return !h ? -1 : h->chain ? 2 : h->mid4 ? 3 : 0; }
+int gnn_mlp_tile_merge_state(const gnn_mlp_t *h) { return !h ? -1 : (h->chain && h->ts_merge && h->rb && !h->group && !h->env_tile_head_off) ? h->ts_merge_tiles : 0; }
 int gnn_mlp_rowblock_state(const gnn_mlp_t *h) { return !h ? -1 : !h->rb ? 0 : h->rb_jit ? 3 : h->rb_static ? 2 : 1; }
 const char *gnn_mlp_plan_note(const gnn_mlp_t *h) { return h ? h->plan_note.c_str() : ""; }
 

@@ -71,6 +71,7 @@ __device__ __forceinline__ const int32_t *group_rel(const int32_t *q, const Grou
 // twins have no head arguments, tile_step_kernel.h, and compile to the code they had before the single-net kernels got theirs)
 #define TS_HEAD_PROLOGUE 0
 #define TS_DEFER_WV 0
+#define TS_MERGE_KINDS 0 // (the merged map's workgroup kinds: single-net f32 only)
 #define TS_HAS_ROW_IDX TS_REL(p.row_idx)
 #define TS_STAGE_N L.N
 #define TS_BID blockIdx.x
@@ -128,6 +129,7 @@ __global__ __launch_bounds__(TS_THREADS) void tile_step_bf16_group_sized_kernel(
 }
 #undef TS_HEAD_PROLOGUE
 #undef TS_DEFER_WV
+#undef TS_MERGE_KINDS
 #undef TS_HAS_ROW_IDX
 #undef TS_STAGE_N
 #undef TS_BID

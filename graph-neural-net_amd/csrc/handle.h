@@ -132,6 +132,9 @@ struct gnn_mlp {
     uint32_t *ts_map = nullptr, *ts_map0 = nullptr; // workgroup -> tile of the two grids (make_tile_map), device memory
     bool ts_map_args = false; uint32_t ts_map_words[2][gnn::TS_MAP_ARGS / 2]; // ... and packed for the kernel arguments ([0]: all layers, [1]: layer 0)
     gnn::TileHead ts_head[2] = {{0, 0}, {0, 0}}; // the two words that name the regular slots' tiles without a lookup (make_tile_head; {0, 0}: the plan is not regular), same order
+    // the merged map of the training form (make_merged_tile_map: light tiles share a workgroup, no CU runs two), kept beside
+    // the map above; packed words only.  ts_merge: it is usable -- one entry per CU at most, the words hold it, single f32 net
+    bool ts_merge = false; int ts_merge_tiles = 0; uint32_t ts_merge_words[gnn::TS_MAP_ARGS / 2]; gnn::TileHead ts_merge_head = {0, 0};
     float *slabs = nullptr;
     int n_slabs = 0;
     std::string plan_note;    // why the net is NOT on the two-launch path (empty when it is): gnn_mlp_plan_note
@@ -204,6 +207,7 @@ struct gnn_mlp {
     bool env_chain_off = false;  // GNN_MLP_CHAIN=0: three launches per step (fwd_first / middle4 / grad_update)
     int first_wavek_rows = 256;  // launch_fwd_first: blocks of at least this many rows take the (ragged) wave-K GEMM (GNN_MLP_FIRST_WAVEK_ROWS; 0 = never)
     int first_gemm_rows = 2048;  // launch_fwd_first: blocks of at least this many rows take gemm_f32_kernel (GNN_MLP_FIRST_GEMM_ROWS; 0 = never)
+    bool env_tile_merge_off = false; // GNN_MLP_TILE_MERGE=0: the tile kernel's training launch on the one-tile-per-workgroup map and kernel, as before the merged map
     bool env_tile_head_off = false; // GNN_MLP_TILE_HEAD=0: the tile kernel's earlier prologue -- every argument from the struct, every tile from the lookup, W and V requested at the top
     bool env_rb_off = false;     // GNN_MLP_ROWBLOCK=0: middle4_kernel<.., SLABS> as the two-launch step's row-block kernel (round 2's form)
 };

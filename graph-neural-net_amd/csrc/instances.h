@@ -92,5 +92,9 @@ template <class Fam> const void *tile_step_instance(int gsrc, int gdst, bool fwd
     else return nullptr;
 }
 
+// the ONE instance that knows the workgroup kinds of the merged map (tile_step_kernel.h, make_merged_tile_map): the training
+// form <1, 2, true> of a single f32 net with the head prologue.  Every other form keeps the one-tile-per-workgroup map.
+template <class Fam> const void *tile_step_merged_instance() { return Fam::merged(); }
+
 } // namespace host
 } // namespace gnn

@@ -172,6 +172,7 @@ void fused_forward(gnn_mlp *h, const float *a0, const float *y, int B, bool back
 template <bool HEAD> struct TileF32 {
     static constexpr bool kPeerForms = true;
     template <int S, int D, bool F> static const void *fn() { return GNN_KERNEL(tile_step_kernel<S, D, F, HEAD, HEAD>); }
+    static const void *merged() { static_assert(HEAD, "the merged kinds have the head prologue only"); return GNN_KERNEL(tile_step_kernel<1, 2, true, true, true, true, true>); }
 };
 template <bool HEAD> struct TileBf16 {
     static constexpr bool kPeerForms = true;
@@ -211,6 +212,17 @@ void launch_tile_step(gnn_mlp *h, int gsrc, int gdst, const NextBatch *next, con
     }
     if (h->grp) { launch_tile_step_group(h, gsrc, gdst, fwd, grid.x, t, B); return; } // every member of a group (group_kernels.hip)
     const bool bf = h->dtype == GNN_DTYPE_BF16, head = !h->env_tile_head_off;
+    // The training form of a single f32 net on the row-block kernel's path: the merged map and the instance that knows its
+    // workgroup kinds, when the plan kept one (plan.hip: at most one workgroup per CU).  Same results, tile for tile.
+    if (h->ts_merge && h->rb && !bf && !h->group && head && gsrc == 1 && gdst == 2 && fwd && !t.stage_out) {
+        std::memcpy(t.map_words, h->ts_merge_words, sizeof(t.map_words));
+        t.map_in_args = 1;
+        int hd_Kr = t.K | (t.row_idx ? 1 : 0);
+        TileHead hd = h->ts_merge_head;
+        void *args[] = {&t.layer[0].A, &t.layer[0].D, &t.layer[0].W, &t.layer[0].V, &t.layer[0].lda, &t.layer[0].ldd, &t.layer[0].M, &hd_Kr, &hd.geo, &hd.kx, &t};
+        launch_instance(h, cls, tile_step_merged_instance<TileF32<true>>(), nullptr, dim3((unsigned)h->ts_merge_tiles), block, 0, args);
+        return;
+    }
     const void *fn = bf ? (head ? tile_step_instance<TileBf16<true>>(gsrc, gdst, fwd) : tile_step_instance<TileBf16<false>>(gsrc, gdst, fwd))
                         : (head ? tile_step_instance<TileF32<true>>(gsrc, gdst, fwd) : tile_step_instance<TileF32<false>>(gsrc, gdst, fwd));
     // (the head arguments: tile_step_kernel.h, GNN_TS_HEAD_PARAMS -- in this order; the bf16 kernel takes layer 0's bf16 A and D in the first two slots)

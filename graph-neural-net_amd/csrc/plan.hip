@@ -77,6 +77,7 @@ void plan_chain(gnn_mlp *h) {
     h->chain = false;
     h->n_slabs = 0;
     h->tsp = TileStepParams{};
+    h->ts_merge = false;
     if (h->env_chain_off) { h->plan_note = "two-launch path switched off (GNN_MLP_CHAIN=0)"; return; }
     if (!h->mid4) return; // (plan_mid4 said why)
     const int L = h->L;
@@ -141,6 +142,17 @@ void plan_chain(gnn_mlp *h) {
         // the regular slots' decode words, each checked slot by slot against its map ({0, 0} = every slot by lookup)
         h->ts_head[0] = make_tile_head(ml, all);
         h->ts_head[1] = make_tile_head(ml, first);
+        // the merged map of the training form, beside the one above (launch_tile_step chooses): kept when no XCD holds more
+        // entries than it has CUs and the packed words hold it; a single f32 net only
+        if (h->dtype != GNN_DTYPE_BF16 && !t_arena && !h->env_tile_merge_off) {
+            bool usable = false;
+            const std::vector<uint32_t> merged = make_merged_tile_map(ml, L - 1, cus / 8, usable);
+            if (usable && !merged.empty() && pack_tile_map(merged, h->ts_merge_words)) {
+                h->ts_merge = true;
+                h->ts_merge_tiles = (int)merged.size();
+                h->ts_merge_head = make_tile_head(ml, merged);
+            }
+        }
     }
     t.slabs = h->slabs; t.slab_rows = h->cap_rows; t.ldz = h->ld[1];
     h->chain = true;

@@ -1,6 +1,7 @@
 // tile_step_body.inc -- the body of tile_step_kernel (tile_step_kernel.h), included INSIDE the kernels that run it:
 // the single-net kernel and its grouped twin (group_kernels.h).  In scope: the kernel argument `p` (TileStepParams),
-// the template parameters GSRC / GDST / FWD, TS_HEAD_PROLOGUE / TS_HEAD / TS_DEFER_WV / TS_LOOKUP1 / TS_HAS_ROW_IDX (tile_step_kernel.h), and nine macros that say who the kernel works for:
+// the template parameters GSRC / GDST / FWD, TS_HEAD_PROLOGUE / TS_HEAD / TS_DEFER_WV / TS_LOOKUP1 / TS_HAS_ROW_IDX (tile_step_kernel.h), TS_MERGE_KINDS (and, where it is 1, TS_MERGE: the
+// workgroup kinds of the merged map, in one single-net instance; 0 in the grouped twins), and nine macros that say who the kernel works for:
 // TS_BID (the workgroup's index in the tile map), TS_REL(ptr) (the net's copy of a pointer of `p`), TS_REL_LAYER(L) (the same
 // for a layer descriptor), TS_STEP_OVER_B and TS_MOMENTUM, and the four row counts TS_K / TS_K_TRUE (the current batch, padded /
 // live) and TS_NEXT_K / TS_NEXT_ROWS (the next one).  The single-net kernels define them as the plain expressions
@@ -12,7 +13,12 @@
     constexpr int LDD = TS_TN;       // delta image [k][n]: 16 floats (lanes 16-31 land on banks 16-31)
     constexpr int LDW = TS_TN + 4;   // weight tile / partial tiles [m][n]
     __shared__ __attribute__((aligned(16))) float sA[TS_KC * LDA];       // A chunk [128][64]
-    __shared__ __attribute__((aligned(16))) float sD[TS_KC * LDD];       // delta chunk [128][16]
+#if TS_MERGE_KINDS
+    constexpr int SD_IMAGES = TS_MERGE ? 2 : 1; // (the merged kinds below keep two [128][16] images side by side: +8 KB)
+#else
+    constexpr int SD_IMAGES = 1;
+#endif
+    __shared__ __attribute__((aligned(16))) float sD[SD_IMAGES * TS_KC * LDD]; // delta chunk [128][16]
     __shared__ __attribute__((aligned(16))) float sW[TS_TM * LDW];       // the tile's (new) weights (53 KB in all)
     const int t = threadIdx.x, lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -47,6 +53,9 @@
         //  uses them, behind the wait for the word -- the second trip again)
         asm volatile("" ::"s"(w), "s"(in_args), "s"(L1.A), "s"(L1.D), "s"(L1.W), "s"(L1.V), "s"(L1.lda), "s"(L1.ldd), "s"(L1.M));
         if (GSRC >= 2 || GDST == 1) asm volatile("" ::"s"(L1.G));
+#if TS_MERGE_KINDS
+        if (TS_MERGE) asm volatile("" ::"s"(L1.N), "s"(L.N)); // (the merged kinds clip their columns at the layer's width)
+#endif
         uint32_t e = (TS_BID & 1) ? w >> 16 : w & 0xffffu;
         li = (int)(e & 7u); tm = (int)((e >> 3) & 63u); tn = (int)(e >> 9);
         bool idle = e == 0xffffu;
@@ -79,6 +88,252 @@
     TS_REL_LAYER(L);
     const int m0 = tm * TS_TM, n0 = tn * TS_TN;
     const bool fwd = FWD && li == 0; // block-uniform
+
+#if TS_MERGE_KINDS
+    // ---- the workgroup kinds of make_merged_tile_map (tile_step_kernel.h): several light tiles in one workgroup ------------
+    // Every tile's sums are the ones it has on the path below, operation for operation: the same MFMAs on acc0 / acc1 over the
+    // same trips, the same update, the same z0 + z1 of a slab piece (the MFMAs a partial-row tile spends on its zero padding are
+    // not issued: they add +0 to sums that start at +0).  Only who computes a tile changes.  A whole layer-0 tile goes on below.
+    static_assert(!TS_MERGE || (GSRC == 1 && GDST == 2 && FWD && TS_HEAD && TS_DEFER_WV), "the merged kinds exist for the training form only");
+    if (TS_MERGE && (li != 0 || L.M - m0 <= TS_TM / 2)) {
+        constexpr int SDI = TS_KC * LDD; // floats of one [128][16] image in sD
+        const int tiles_n = L.N / TS_TN, kc0 = (TS_K < TS_KC) ? TS_K : TS_KC;
+        // the gradient loop of the path below on two operand images: x the delta operand, y the A operand
+        auto grad_loop = [&](const float *xp, const int ldx, const float *yp, const int ldy, const int kc, f32x4 &acc0, f32x4 &acc1) __attribute__((always_inline)) {
+            int kk = 0;
+            if (kc == TS_KC) {
+                float x[2][8], y[2][8];
+#pragma unroll
+                for (int j = 0; j < 8; j++) { x[0][j] = xp[(4 * j) * ldx]; y[0][j] = yp[(4 * j) * ldy]; }
+#pragma unroll
+                for (int trip = 0; trip < TS_KC / 32; trip++) {
+                    const int cur = trip & 1;
+                    if (trip + 1 < TS_KC / 32) {
+#pragma unroll
+                        for (int j = 0; j < 8; j++) { x[cur ^ 1][j] = xp[(32 * (trip + 1) + 4 * j) * ldx]; y[cur ^ 1][j] = yp[(32 * (trip + 1) + 4 * j) * ldy]; }
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int j = 0; j < 8; j += 2) {
+                        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(x[cur][j], y[cur][j], acc0, 0, 0, 0);
+                        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(x[cur][j + 1], y[cur][j + 1], acc1, 0, 0, 0);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                kk = TS_KC;
+            }
+            for (; kk + 32 <= kc; kk += 32) {
+                float x[8], y[8];
+#pragma unroll
+                for (int j = 0; j < 8; j++) { x[j] = xp[(kk + 4 * j) * ldx]; y[j] = yp[(kk + 4 * j) * ldy]; }
+#pragma unroll
+                for (int j = 0; j < 8; j += 2) {
+                    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(x[j], y[j], acc0, 0, 0, 0);
+                    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(x[j + 1], y[j + 1], acc1, 0, 0, 0);
+                }
+            }
+            for (; kk < kc; kk += 4)
+                acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(xp[kk * ldx], yp[kk * ldy], acc0, 0, 0, 0);
+        };
+        auto update = [&](const f32x4 acc, const float4 w_old, const float4 v_old, const size_t e_off, const bool e_ok) __attribute__((always_inline)) {
+            float4 adj;
+            adj.x = sgd_adj(TS_STEP_OVER_B, acc[0], TS_MOMENTUM, v_old.x);
+            adj.y = sgd_adj(TS_STEP_OVER_B, acc[1], TS_MOMENTUM, v_old.y);
+            adj.z = sgd_adj(TS_STEP_OVER_B, acc[2], TS_MOMENTUM, v_old.z);
+            adj.w = sgd_adj(TS_STEP_OVER_B, acc[3], TS_MOMENTUM, v_old.w);
+            const float4 w_new = make_float4(w_old.x - adj.x, w_old.y - adj.y, w_old.z - adj.z, w_old.w - adj.w);
+            if (e_ok) {
+                ts_store16(L.W + e_off, (f32x4){w_new.x, w_new.y, w_new.z, w_new.w});
+                ts_store16(L.V + e_off, (f32x4){adj.x, adj.y, adj.z, adj.w});
+            }
+            return w_new;
+        };
+        const bool wide = (unsigned long long)TS_KC * (unsigned)(L.lda > L.ldd ? L.lda : L.ldd) >= 0xffffffffull; // no 32-bit offsets
+
+        if (li != 0) {
+            // -- a pair of a later layer: columns tn and tn + 1 of one tile row.  The A chunk is loaded and staged once; waves
+            //    0..3 run the gradient loop on column tn, waves 4..7 on column tn + 1 (the second image of sD); all 512 threads
+            //    update 16 B of W / V.  No forward half.
+            const int ncol = ts_merged_columns(li, 0, tn, tiles_n); // 2, or 1 at the end of an odd row
+            const int half = wave >> 2, er = (wave & 3) * 16 + fr;
+            const bool e_ok = m0 + er < L.M && half < ncol;
+            const size_t e_off = (size_t)(m0 + er) * L.ldd + n0 + half * TS_TN + fq * 4;
+            float4 va[4], vd[2];
+            auto load_ops = [&](const int k0, const int kc, const bool plain) __attribute__((always_inline)) {
+                if (plain) { // (block-uniform) a whole chunk of a whole tile, both columns: no bounds tests
+#pragma unroll
+                    for (int i = 0; i < 4; i++) {
+                        const int idx = t + i * NT, k = idx >> 4, q = idx & 15;
+                        va[i] = *reinterpret_cast<const float4 *>(L.A + ((unsigned)k * (unsigned)L.lda + m0 + q * 4));
+                    }
+#pragma unroll
+                    for (int c = 0; c < 2; c++)
+                        vd[c] = *reinterpret_cast<const float4 *>(L.D + ((unsigned)(t >> 2) * (unsigned)L.ldd + n0 + c * TS_TN + (t & 3) * 4));
+                    return;
+                }
+#pragma unroll
+                for (int i = 0; i < 4; i++) {
+                    const int idx = t + i * NT, k = idx >> 4, q = idx & 15;
+                    va[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+                    if (k < kc && m0 + q * 4 < L.M) va[i] = *reinterpret_cast<const float4 *>(L.A + (size_t)(k0 + k) * L.lda + m0 + q * 4);
+                }
+#pragma unroll
+                for (int c = 0; c < 2; c++) {
+                    vd[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+                    if ((t >> 2) < kc && c < ncol) vd[c] = *reinterpret_cast<const float4 *>(L.D + (size_t)(k0 + (t >> 2)) * L.ldd + n0 + c * TS_TN + (t & 3) * 4);
+                }
+            };
+            load_ops(0, kc0, (m0 + TS_TM <= L.M) && TS_K >= TS_KC && ncol == 2 && !wide);
+            TS_STAMP(1);
+            float4 w_old = make_float4(0.f, 0.f, 0.f, 0.f), v_old = make_float4(0.f, 0.f, 0.f, 0.f);
+            f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+            for (int k0 = 0; k0 < TS_K; k0 += TS_KC) {
+                const int kc = (TS_K - k0 < TS_KC) ? TS_K - k0 : TS_KC;
+                if (k0) { __syncthreads(); load_ops(k0, kc, false); }
+#pragma unroll
+                for (int i = 0; i < 4; i++) {
+                    const int idx = t + i * NT, k = idx >> 4, q = idx & 15;
+                    *reinterpret_cast<float4 *>(&sA[k * LDA + q * 4]) = va[i];
+                }
+#pragma unroll
+                for (int c = 0; c < 2; c++) *reinterpret_cast<float4 *>(&sD[c * SDI + (t >> 2) * LDD + (t & 3) * 4]) = vd[c];
+                __syncthreads();
+                if (k0 == 0) {
+                    TS_STAMP(2);
+                    if (e_ok) { w_old = *reinterpret_cast<const float4 *>(L.W + e_off); v_old = *reinterpret_cast<const float4 *>(L.V + e_off); }
+                }
+                if (half < ncol) grad_loop(&sD[half * SDI + fq * LDD + fr], LDD, &sA[fq * LDA + (wave & 3) * 16 + fr], LDA, kc, acc0, acc1); // (wave-uniform)
+            }
+            update(acc0 + acc1, w_old, v_old, e_off, e_ok);
+            TS_STAMP(3);
+            return;
+        }
+
+        // -- a group of layer 0's partial last tile row, h = 16 or 32 weight rows: 64 / h adjacent column tiles.  The two images
+        //    swap roles: the h-wide A chunk goes where sD is (one [128][16] image per m tile), the delta chunk of all the group's
+        //    columns where sA is.  Wave w of 0..3 runs the gradient loop for column tile w / (h / 16), m tile w % (h / 16); in
+        //    the forward half every wave keeps its 16 rows of the next batch, h inputs wide, and forms one slab piece per column
+        //    tile from sW, which holds the group's new weights.
+        // (one body per height, MTS = h / 16 m tiles: every count below is a constant of its instance)
+        auto group = [&](auto mts_c) __attribute__((always_inline)) {
+            constexpr int MTS = decltype(mts_c)::value, H = 16 * MTS, NCOL = TS_TM / H; // m tiles; rows; column tiles of a full group
+            constexpr int ASH = MTS == 2 ? 3 : 2, DSH = MTS == 2 ? 3 : 4;               // float4s per row of the A chunk / of the delta chunk, as shifts
+            const int ncol = ts_merged_columns(0, H, tn, tiles_n);                      // column tiles owned
+            const int gc = MTS == 2 ? wave >> 1 : wave, gm = MTS == 2 ? wave & 1 : 0;   // (waves 0..3)
+            const int er = gm * 16 + fr;
+            const bool e_ok = wave < 4 && gc < ncol;
+            const size_t e_off = (size_t)(m0 + er) * L.ldd + n0 + gc * TS_TN + fq * 4;
+            float4 va[MTS], vd[NCOL];
+            auto load_ops = [&](const int k0, const int kc, const bool plain) __attribute__((always_inline)) {
+                if (plain) { // (block-uniform) a whole chunk, rows in place, every column of a full group: no bounds tests
+#pragma unroll
+                    for (int i = 0; i < MTS; i++) {
+                        const int idx = t + i * NT, k = idx >> ASH, q = idx & ((1 << ASH) - 1);
+                        va[i] = *reinterpret_cast<const float4 *>(L.A + ((unsigned)k * (unsigned)L.lda + m0 + q * 4));
+                    }
+#pragma unroll
+                    for (int i = 0; i < NCOL; i++) {
+                        const int idx = t + i * NT, k = idx >> DSH, q = idx & ((1 << DSH) - 1);
+                        vd[i] = *reinterpret_cast<const float4 *>(L.D + ((unsigned)k * (unsigned)L.ldd + n0 + q * 4));
+                    }
+                    return;
+                }
+#pragma unroll
+                for (int i = 0; i < MTS; i++) {
+                    const int idx = t + i * NT, k = idx >> ASH, q = idx & ((1 << ASH) - 1);
+                    va[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+                    if (k < kc) {
+                        size_t a_row = (size_t)(k0 + k);
+                        bool live = true;
+                        if (TS_REL(p.row_idx)) { live = k0 + k < TS_K_TRUE; a_row = live ? (size_t)TS_REL(p.row_idx)[k0 + k] : 0; }
+                        if (live) va[i] = *reinterpret_cast<const float4 *>(L.A + a_row * L.lda + m0 + q * 4);
+                    }
+                }
+#pragma unroll
+                for (int i = 0; i < NCOL; i++) {
+                    const int idx = t + i * NT, k = idx >> DSH, q = idx & ((1 << DSH) - 1);
+                    vd[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+                    if (k < kc && q * 4 < ncol * TS_TN) vd[i] = *reinterpret_cast<const float4 *>(L.D + (size_t)(k0 + k) * L.ldd + n0 + q * 4);
+                }
+            };
+            load_ops(0, kc0, TS_K >= TS_KC && !TS_HAS_ROW_IDX && ncol == NCOL && !wide);
+            TS_STAMP(1);
+            // the next batch's rows of this wave, H inputs wide, in fragment form (as vn below)
+            f32x4 vn[MTS];
+            int next_row0 = wave * 16 + fr;
+            if (TS_REL(p.next_idx) && next_row0 < TS_NEXT_ROWS) next_row0 = TS_REL(p.next_idx)[next_row0];
+            auto load_next = [&](const int b0) __attribute__((always_inline)) {
+                const int b = b0 + wave * 16 + fr;
+                const bool live = b < TS_NEXT_ROWS;
+                const size_t row = live ? (b0 == 0 ? (size_t)next_row0 : TS_REL(p.next_idx) ? (size_t)TS_REL(p.next_idx)[b] : (size_t)b) : 0;
+                const float *src = TS_REL(p.An) + row * p.ldan + m0 + 4 * fq;
+#pragma unroll
+                for (int c = 0; c < MTS; c++) {
+                    vn[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
+                    if (live) vn[c] = *reinterpret_cast<const f32x4 *>(src + c * 16);
+                }
+            };
+            float4 w_old = make_float4(0.f, 0.f, 0.f, 0.f), v_old = make_float4(0.f, 0.f, 0.f, 0.f);
+            f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+            for (int k0 = 0; k0 < TS_K; k0 += TS_KC) {
+                const int kc = (TS_K - k0 < TS_KC) ? TS_K - k0 : TS_KC;
+                if (k0) { __syncthreads(); load_ops(k0, kc, false); }
+#pragma unroll
+                for (int i = 0; i < MTS; i++) {
+                    const int idx = t + i * NT, k = idx >> ASH, q = idx & ((1 << ASH) - 1);
+                    *reinterpret_cast<float4 *>(&sD[(q >> 2) * SDI + k * LDD + (q & 3) * 4]) = va[i];
+                }
+#pragma unroll
+                for (int i = 0; i < NCOL; i++) {
+                    const int idx = t + i * NT, k = idx >> DSH, q = idx & ((1 << DSH) - 1);
+                    *reinterpret_cast<float4 *>(&sA[k * LDA + q * 4]) = vd[i];
+                }
+                __syncthreads();
+                if (k0 == 0) {
+                    TS_STAMP(2);
+                    if (e_ok) { w_old = *reinterpret_cast<const float4 *>(L.W + e_off); v_old = *reinterpret_cast<const float4 *>(L.V + e_off); }
+                    load_next(0);
+                }
+                if (e_ok) grad_loop(&sA[fq * LDA + gc * TS_TN + fr], LDA, &sD[gm * SDI + fq * LDD + fr], LDD, kc, acc0, acc1); // (wave-uniform)
+            }
+            const float4 w_new = update(acc0 + acc1, w_old, v_old, e_off, e_ok);
+            TS_STAMP(3);
+            // sW: [column tile][H rows][LDW]; the rows of a column tile the group does not own (a short last group) are zeros
+            if (wave < 4) *reinterpret_cast<float4 *>(&sW[((gc * MTS + gm) * 16 + fr) * LDW + fq * 4]) = e_ok ? w_new : make_float4(0.f, 0.f, 0.f, 0.f);
+            __syncthreads();
+            float *slab = TS_REL(p.slabs) + (size_t)tm * p.slab_rows * p.ldz;
+            float wv[NCOL][MTS][4]; // [column tile][16-input chunk][j]: W[m = 16 c + 4 fq + j][n = fr] of column tile cc
+#pragma unroll
+            for (int cc = 0; cc < NCOL; cc++)
+#pragma unroll
+                for (int c = 0; c < MTS; c++)
+#pragma unroll
+                    for (int j = 0; j < 4; j++) wv[cc][c][j] = sW[(cc * H + c * 16 + 4 * fq + j) * LDW + fr];
+            for (int b0 = 0; b0 < TS_NEXT_K; b0 += TS_KC) {
+                if (b0) load_next(b0);
+                const int wr = wave * 16;
+                if (b0 + wr < TS_NEXT_K) { // wave-uniform
+#pragma unroll
+                    for (int cc = 0; cc < NCOL; cc++) {
+                        f32x4 z0 = {0.f, 0.f, 0.f, 0.f}, z1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                        for (int j = 0; j < 4; j++) z0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[cc][0][j], vn[0][j], z0, 0, 0, 0);
+                        if (MTS == 2) {
+#pragma unroll
+                            for (int j = 0; j < 4; j++) z1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[cc][MTS - 1][j], vn[MTS - 1][j], z1, 0, 0, 0);
+                        }
+                        const f32x4 z = z0 + z1;
+                        if (cc < ncol) ts_store16(slab + (size_t)(b0 + wr + fr) * p.ldz + n0 + cc * TS_TN + 4 * fq, z); // (block-uniform)
+                    }
+                }
+            }
+            TS_STAMP(3);
+        };
+        if (L.M - m0 == 16) group(ts_int<1>{});
+        else group(ts_int<2>{});
+        return;
+    }
+#endif
 
     // this thread's 16 B of the weight tile (waves 0..3): row er = 16*wave + fr, columns 4*fq .. 4*fq+3 -- the
     // accumulator layout of the transposed gradient product below, so G never leaves its registers

@@ -219,6 +219,65 @@ inline TileHead make_tile_head(const TileMapLayer *layers, const std::vector<uin
     return hd;
 }
 
+// ---- the merged map: light tiles share a workgroup, so that no CU runs two -----------------------------------------
+// make_tile_map gives 784-300-100-10 284 live workgroups for 256 CUs, and the second workgroup of a shared CU decides when
+// the kernel ends.  The light tiles do not fill a workgroup: a tile of layer 0's partial last tile row (16 or 32 weight rows)
+// uses one or two of the four gradient waves, a tile of a later layer has no forward half.  Here
+//   * a whole layer-0 tile (more than 32 rows) keeps its workgroup and the XCD of its rectangle, in rectangle order;
+//   * the partial last tile row of layer 0, h = 16 or 32 rows high: one workgroup owns 64 / h adjacent column tiles (the last
+//     group of the row may be short); the entry names the first of them;
+//   * a later layer: one workgroup owns columns tn and tn + 1 of one tile row, tn even (the last column of an odd count
+//     stays single);
+// and every unit that is not a whole layer-0 tile goes to the XCD with the fewest entries, behind that XCD's whole tiles.
+// The entry formats are make_tile_map's; which kind a slot is follows from (layer, tile row) and how many columns it owns
+// from the layer's width (ts_merged_columns).  usable: no XCD holds more than cus_per_xcd entries, so that a grid of the
+// map's size puts one workgroup on a CU; a map that is not usable is still complete, and not launched (plan.hip).
+// 784-300-100-10: 228 + 5 + 20 + 2 = 255 entries in a grid of 256.
+template <int V> struct ts_int { static constexpr int value = V; }; // (a count as a type: tile_step_body.inc, one body per height of a group)
+__host__ __device__ __forceinline__ int ts_merged_columns(int li, int rows, int tn, int tiles_n) { // columns the unit at (li, tn) owns; rows: the tile row's height
+    const int want = li != 0 ? 2 : rows <= TS_TM / 4 ? 4 : rows <= TS_TM / 2 ? 2 : 1;
+    return tiles_n - tn < want ? tiles_n - tn : want;
+}
+inline std::vector<uint32_t> make_merged_tile_map(const TileMapLayer *layers, int n_layers, int cus_per_xcd, bool &usable) {
+    struct T { uint32_t e; int w; };
+    std::vector<uint32_t> per_xcd[8];
+    long load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    std::vector<T> light;
+    for (int l = 0; l < n_layers; l++) {
+        const int tiles_m = (layers[l].M + TS_TM - 1) / TS_TM, tiles_n = layers[l].N / TS_TN;
+        int full_m = 0; // (as in make_tile_map)
+        if (l == 0) for (int tm = 0; tm < tiles_m; tm++) if (layers[l].M - tm * TS_TM > TS_TM / 2) full_m = tm + 1;
+        const XcdTiling rect = full_m > 0 ? make_xcd_tiling(full_m, tiles_n) : XcdTiling{};
+        for (int tm = 0; tm < tiles_m; tm++) {
+            const int rows = layers[l].M - tm * TS_TM < TS_TM ? layers[l].M - tm * TS_TM : TS_TM;
+            const bool whole = l == 0 && tm < full_m;
+            for (int tn = 0; tn < tiles_n; tn += whole ? 1 : ts_merged_columns(l, rows, tn, tiles_n)) {
+                const uint32_t e = (uint32_t)l | (uint32_t)tm << 4 | (uint32_t)tn << 18;
+                if (whole) {
+                    const int x = (tm / rect.rm) * rect.xn + tn / rect.rn;
+                    per_xcd[x].push_back(e);
+                    load[x] += 100 + rows / 4;
+                } else light.push_back(T{e, (l == 0 ? 100 : 0) + rows * ts_merged_columns(l, rows, tn, tiles_n) / 4});
+            }
+        }
+    }
+    std::stable_sort(light.begin(), light.end(), [](const T &a, const T &b) { return a.w > b.w; });
+    for (const T &t : light) { // heaviest first, each to the XCD with the fewest entries (ties: the least work, then the lowest id)
+        int best = 0;
+        for (int x = 1; x < 8; x++)
+            if (per_xcd[x].size() < per_xcd[best].size() || (per_xcd[x].size() == per_xcd[best].size() && load[x] < load[best])) best = x;
+        per_xcd[best].push_back(t.e);
+        load[best] += t.w;
+    }
+    size_t slots = 0;
+    for (int x = 0; x < 8; x++) slots = per_xcd[x].size() > slots ? per_xcd[x].size() : slots;
+    usable = slots <= (size_t)cus_per_xcd;
+    std::vector<uint32_t> map(slots * 8, ~0u);
+    for (int x = 0; x < 8; x++)
+        for (size_t j = 0; j < per_xcd[x].size(); j++) map[j * 8 + x] = per_xcd[x][j];
+    return map;
+}
+
 // 16-B store that is written THROUGH the XCD's L2 (sc1): the line does not stay dirty, so the end of the kernel has nothing
 // to write back for it (a kernel boundary costs ~B / 6 TB/s for B dirty bytes, MI355X_MICROARCH.md, row `boundary`), and the
 // bytes leave while the kernel still runs.  Inline asm (the compiler has no spelling for it on a 16-B vector); the s_nop
@@ -276,6 +335,10 @@ template <int GSRC> __device__ __forceinline__ float4 ts_gradient_in(const TileS
 #define TS_HEAD HEAD
 #define TS_DEFER_WV DEFER_WV
 #define TS_LOOKUP1 LOOKUP1
+// MERGE: the workgroup kinds of make_merged_tile_map (tile_step_body.inc, TS_MERGE_KINDS) -- on in ONE instance, the f32
+// training form <1, 2, true> of a single net (launch_small.hip); every other instance compiles to the code it had
+#define TS_MERGE_KINDS 1
+#define TS_MERGE MERGE
 #ifndef TS_STAMP
 #define TS_STAMP(slot) // (tools/tile_probe.hip defines it in its stamped build; nothing is stamped in the library)
 #endif
@@ -290,7 +353,7 @@ template <int GSRC> __device__ __forceinline__ float4 ts_gradient_in(const TileS
 #define TS_STAGE_N p.layer[0].N // (layer 0's N where it is used, behind the barrier: as a field of L its scalar load was waited for at the top)
 #define TS_NEXT_ROWS p.next_rows
 #define TS_NEXT_K p.next_K
-template <int GSRC, int GDST, bool FWD, bool HEAD = true, bool DEFER_WV = true, bool LOOKUP1 = HEAD>
+template <int GSRC, int GDST, bool FWD, bool HEAD = true, bool DEFER_WV = true, bool LOOKUP1 = HEAD, bool MERGE = false>
 __global__ __launch_bounds__(TS_THREADS) void tile_step_kernel(GNN_TS_HEAD_PARAMS, TileStepParams p) {
 #include "tile_step_body.inc"
 }
@@ -312,6 +375,8 @@ __global__ __launch_bounds__(TS_THREADS) void tile_step_bf16_kernel(GNN_TS_HEAD_
 #undef TS_HEAD
 #undef TS_DEFER_WV
 #undef TS_LOOKUP1
+#undef TS_MERGE_KINDS
+#undef TS_MERGE
 #undef TS_HAS_ROW_IDX
 #undef TS_STAGE_N
 #undef TS_BID

@@ -470,6 +470,11 @@ class NeuralNet:
         return self._lib.gnn_mlp_rowblock_state(self._h)
 
     @property
+    def tile_merge_state(self):
+        """The tile kernel's training launch: 0 one tile per workgroup, n > 0 the merged map in a grid of n workgroups."""
+        return self._lib.gnn_mlp_tile_merge_state(self._h)
+
+    @property
     def plan_note(self):
         """Why the net is not on the two-launch path ('' when it is)."""
         s = self._lib.gnn_mlp_plan_note(self._h)

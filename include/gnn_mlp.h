@@ -511,6 +511,10 @@ int gnn_mlp_step_launches(const gnn_mlp_t *h);
  * fit, GNN_MLP_ROWBLOCK=0: the step then uses middle4_kernel), 1 = runtime-shape instantiation, 2 = prebuilt for the shape,
  * 3 = instantiated at run time for the shape (gnn_mlp_specialize / the 16th step). */
 int gnn_mlp_rowblock_state(const gnn_mlp_t *h);
+/* The tile-owner kernel's TRAINING launch (gradient + update + next slabs) of this net: 0 = one tile per workgroup, n > 0 = the
+ * merged map (csrc/tile_step_kernel.h, make_merged_tile_map: light tiles share a workgroup, no CU runs two) in a grid of n
+ * workgroups.  0 for bf16, group members, a net with more units than CUs, off the row-block kernel's path, GNN_MLP_TILE_MERGE=0. */
+int gnn_mlp_tile_merge_state(const gnn_mlp_t *h);
 /* Why gnn_mlp_step_launches() is not 2 for this net ("" when it is): the decision gnn_mlp_create took (layer count,
  * LDS budget, slab count, a failed allocation, a GNN_MLP_* development switch).  The string lives as long as the handle. */
 const char *gnn_mlp_plan_note(const gnn_mlp_t *h);

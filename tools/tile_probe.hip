@@ -1,6 +1,7 @@
 // tile_probe.hip -- development harness (not shipped): tile_step_kernel on the 784-300-100-10 / B = 128
 // shapes with random data: HIP-event time per call of every mode, workgroup -> tile maps and sampled next batches, and the
 // prologue variants (head arguments / W and V behind the first barrier) against the form they replace, in one process.
+// Also the upper bounds (the launch with a class of workgroups taken out of the map) and the merged map and kinds (make_merged_tile_map) against the one-tile launch.
 // Build as the library is built (-mllvm -amdgpu-kernarg-preload-count=16).  -DTILE_PROBE_STAMPS: the stamped build -- thread 0
 // of every workgroup records the cycle counter at the kernel's top, behind its first vector loads, behind the first barrier and
 // at its end; the times of THAT build are not the kernel's (use the plain build's lines), its stamps say where a workgroup's time goes.
@@ -130,6 +131,51 @@ int main(int argc, char **argv) {
         t_nopart.tile_map = to_dev(hm_nopart); t_nopart.map_in_args = pack_tile_map(hm_nopart, t_nopart.map_words) ? 1 : 0;
         t_nopartner.tile_map = to_dev(hm_nopartner); t_nopartner.map_in_args = pack_tile_map(hm_nopartner, t_nopartner.map_words) ? 1 : 0;
         printf("bounds: %d partial-row tiles, %d later-layer tiles that share a CU with a whole layer-0 tile\n", n_part, n_partner);
+        //   one per CU: the partial row AND, of every two live slots that share a CU (j and j + 32 of one XCD), the later-layer
+        //   tile -- no CU runs two workgroups, no XCD more than 32.  Twice: the entries idled in place (the grid and the head words
+        //   of "every tile"), and the live entries of every XCD moved up to the front (a grid of at most 256, head words of its own:
+        //   the launch a merged map would make, with the merged workgroups' work left out)
+        std::vector<uint32_t> hm_one = hm_nopart;
+        int n_one_later = 0, n_one_shared = 0;
+        for (size_t id = 256; id < hm_one.size(); id++) {
+            if (hm_one[id] == ~0u || hm_one[id - 256] == ~0u) continue;
+            if ((hm_one[id] & 15u) != 0) { hm_one[id] = ~0u; n_one_later++; }
+            else if ((hm_one[id - 256] & 15u) != 0) { hm_one[id - 256] = ~0u; n_one_later++; }
+            else n_one_shared++;
+        }
+        std::vector<uint32_t> hm_one_c(hm.size(), ~0u); // (as long as hm for the tables below; launched with its live slots only)
+        int tiles_one = 0, n_one = 0, max_xcd = 0;
+        for (int x = 0; x < 8; x++) {
+            int n = 0;
+            for (size_t id = x; id < hm_one.size(); id += 8) if (hm_one[id] != ~0u) hm_one_c[(size_t)(n++) * 8 + x] = hm_one[id];
+            n_one += n; max_xcd = n > max_xcd ? n : max_xcd;
+        }
+        tiles_one = max_xcd * 8;
+        TileStepParams t_one = t, t_one_c = t;
+        t_one.tile_map = to_dev(hm_one); t_one.map_in_args = pack_tile_map(hm_one, t_one.map_words) ? 1 : 0;
+        t_one_c.tile_map = to_dev(hm_one_c); t_one_c.map_in_args = pack_tile_map(hm_one_c, t_one_c.map_words) ? 1 : 0;
+        const TileHead hd_one_c = make_tile_head(ml, std::vector<uint32_t>(hm_one_c.begin(), hm_one_c.begin() + tiles_one));
+        printf("bounds: one per CU takes out %d partial-row and %d later-layer tiles, %d live of %d (most in one XCD: %d, CUs still shared: %d); moved up: a grid of %d, head words %08x %08x\n",
+               n_part, n_one_later, n_one, tiles, max_xcd, n_one_shared, tiles_one, hd_one_c.geo, hd_one_c.kx);
+        for (int rep = 0; rep < 3; rep++) {
+            time_it("bound: every tile (A + B + C)", 1000, [&]() { LAUNCH((tile_step_kernel<1, 2, true, true, true, true>), tiles, t, hd_all); });
+            time_it("bound: one per CU, idled in place (A + B + C)", 1000, [&]() { LAUNCH((tile_step_kernel<1, 2, true, true, true, true>), tiles, t_one, hd_all); });
+            time_it("bound: one per CU, moved up (A + B + C)", 1000, [&]() { LAUNCH((tile_step_kernel<1, 2, true, true, true, true>), tiles_one, t_one_c, hd_one_c); });
+        }
+        // what was built on that bound: the merged map (make_merged_tile_map: the partial row in groups, the later layers in
+        // pairs, 255 workgroups) and the instance that knows its kinds, against the library's one-tile launch
+        bool mm_usable = false;
+        std::vector<uint32_t> hmm = make_merged_tile_map(ml, 3, 32, mm_usable);
+        const int tiles_m = (int)hmm.size();
+        const TileHead hd_m = make_tile_head(ml, hmm);
+        TileStepParams t_m = t;
+        t_m.tile_map = to_dev(hmm); t_m.map_in_args = pack_tile_map(hmm, t_m.map_words) ? 1 : 0;
+        if (hmm.size() < hm.size()) hmm.resize(hm.size(), ~0u); // (as long as hm for the tables below)
+        printf("merged: a grid of %d, usable %d, packed %d, head words %08x %08x\n", tiles_m, (int)mm_usable, t_m.map_in_args, hd_m.geo, hd_m.kx);
+        for (int rep = 0; rep < 3; rep++) {
+            time_it("merged: one tile per workgroup (the parent's launch)", 1000, [&]() { LAUNCH((tile_step_kernel<1, 2, true, true, true, true>), tiles, t, hd_all); });
+            time_it("merged: the merged map and kinds", 1000, [&]() { LAUNCH((tile_step_kernel<1, 2, true, true, true, true, true>), tiles_m, t_m, hd_m); });
+        }
         for (int rep = 0; rep < 3; rep++) {
             time_it("bound: every tile (A + B)", 1000, [&]() { LAUNCH((tile_step_kernel<1, 2, true, true, true, false>), tiles, t, hd_all); });
             time_it("bound: no partial row", 1000, [&]() { LAUNCH((tile_step_kernel<1, 2, true, true, true, false>), tiles, t_nopart, hd_all); });
@@ -213,6 +259,12 @@ int main(int argc, char **argv) {
         pairs("A + B + C (the library's kernel), with the CUs that hold two workgroups", hm, [&]() { LAUNCH((tile_step_kernel<1, 2, true, true, true, true>), tiles, t, hd_all); });
         classes("bound: no partial row", hm_nopart, [&]() { LAUNCH((tile_step_kernel<1, 2, true, true, true, false>), tiles, t_nopart, hd_all); });
         classes("bound: no partner of a whole tile", hm_nopartner, [&]() { LAUNCH((tile_step_kernel<1, 2, true, true, true, false>), tiles, t_nopartner, hd_all); });
+        for (int rep = 0; rep < 2; rep++) {
+            classes("bound: one per CU, idled in place (A + B + C)", hm_one, [&]() { LAUNCH((tile_step_kernel<1, 2, true, true, true, true>), tiles, t_one, hd_all); });
+            classes("bound: one per CU, moved up (A + B + C)", hm_one_c, [&]() { LAUNCH((tile_step_kernel<1, 2, true, true, true, true>), tiles_one, t_one_c, hd_one_c); });
+        }
+        for (int rep = 0; rep < 3; rep++)
+            classes("merged: the merged map and kinds", hmm, [&]() { LAUNCH((tile_step_kernel<1, 2, true, true, true, true, true>), tiles_m, t_m, hd_m); });
         for (int rep = 0; rep < 2; rep++) {
             stamps("struct + lookup, W/V at the top (before)", [&]() { LAUNCH((tile_step_kernel<1, 2, true, false, false, false>), tiles, t, hd_all); });
             stamps("A  head arguments + decoded tile", [&]() { LAUNCH((tile_step_kernel<1, 2, true, true, false, false>), tiles, t, hd_all); });
