@@ -21,14 +21,14 @@ def act(kind, z):
 
 def act_prime(kind, z):
     if kind == 0:
-        return np.where(z <= 0, 0.01, 1.0)            # MT:235
+        return np.where(z <= 0, 0.01, 1.0).astype(np.asarray(z).dtype)   # MT:235
     if kind == 1:
         s = 1.0 / (1.0 + np.exp(-z))
         return s * (1 - s)
     if kind == 2:
         return 1 - np.tanh(z) ** 2
     if kind == 3:
-        return np.where(z <= 0, 0.0, 1.0)
+        return np.where(z <= 0, 0.0, 1.0).astype(np.asarray(z).dtype)
     return np.ones_like(z)
 
 
@@ -41,9 +41,10 @@ def split(flat, dims):
     return out
 
 
-def forward(Ws, X, inner, out_kind=0, last=1):
-    """Returns pre-activations Z[0..L-1] (Z[0] = X) and the output (SCE:164-198 / GNN:183-221)."""
-    Z = [np.asarray(X, dtype=np.float64)]
+def forward(Ws, X, inner, out_kind=0, last=1, dtype=np.float64):
+    """Returns pre-activations Z[0..L-1] (Z[0] = X) and the output (SCE:164-198 / GNN:183-221).
+    dtype=np.float32 (with float32 Ws): the same formulas carried in float32, a plain restatement of what an f32 device computes."""
+    Z = [np.asarray(X, dtype=dtype)]
     for W in Ws:
         Z.append(act(inner, Z[-1]) @ W)               # f applied to the raw input too (SCE:183-186)
     if out_kind == 0:
@@ -61,9 +62,10 @@ def loss(Ws, X, Y, inner, out_kind=0, last=1):
     return (0.5 * (out - Y) ** 2).sum(axis=1)        # GNN:236-239
 
 
-def gradient(Ws, X, Y, inner, out_kind=0, last=1):
+def gradient(Ws, X, Y, inner, out_kind=0, last=1, dtype=np.float64):
     """Sum over the batch of the per-sample weight gradients, flat (SCE:229-287 + SCE:305-322)."""
-    Z, out = forward(Ws, X, inner, out_kind, last)
+    Z, out = forward(Ws, X, inner, out_kind, last, dtype)
+    Y = np.asarray(Y, dtype=dtype)
     L = len(Ws) + 1
     if out_kind == 0:
         D = out - Y                                   # SCE:249-251
@@ -77,10 +79,10 @@ def gradient(Ws, X, Y, inner, out_kind=0, last=1):
     return np.concatenate([g.ravel() for g in G])
 
 
-def gradient_step(w, v, dims, X, Y, step, momentum, inner, out_kind=0, last=1):
+def gradient_step(w, v, dims, X, Y, step, momentum, inner, out_kind=0, last=1, dtype=np.float64):
     """One gradientStep (SCE:297-346) on flat weights w / momentum v; returns new (w, v)."""
-    g = gradient(split(w, dims), X, Y, inner, out_kind, last)
-    adj = step * g / X.shape[0] + momentum * v        # SCE:333
+    g = gradient(split(w, dims), X, Y, inner, out_kind, last, dtype)
+    adj = dtype(step) * g / dtype(X.shape[0]) + dtype(momentum) * v        # SCE:333
     return w - adj, adj
 
 

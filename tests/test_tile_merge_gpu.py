@@ -1,7 +1,12 @@
 """The tile kernel's training launch on the merged map (csrc/tile_step_kernel.h: make_merged_tile_map; tile_step_body.inc: a
 group of layer 0's partial last tile row, a pair of a later layer, in ONE workgroup) against the same calls with
 GNN_MLP_TILE_MERGE=0 (one tile per workgroup).  Merging changes which workgroup computes a tile and not one operation of the
-tile's sums or their order, so weights and momentum are compared with np.array_equal: no tolerance."""
+tile's sums or their order, so weights and momentum are compared with np.array_equal: no tolerance.
+
+What runs here: three small shapes and the headline one (a 16-row partial row in groups of 4 + 3, a 32-row one in groups of 2 + 1,
+a later layer's 48-row partial tile row), batches of 128, 100, 16 and 144 rows, SoftmaxCrossEntropyNeuralNet with its default
+activation, train_range and one NeuralNetTrainer.  The other geometries, batch sizes, call forms and net classes, and the
+comparison with the fp64 oracle, are in tests/test_tile_merge_cases_gpu.py."""
 import os
 
 import numpy as np
