@@ -320,7 +320,7 @@ int gnn_mlp_group_train_sampled(gnn_mlp_group_t *g, gnn_sampler_t *s, int iterat
     gnn_mlp *h0 = g->m[0];
     TRY(train_sampled_checks(h0, s, iterations, batch, steps[0], noise));
     if (g->K == 1 || !g->grouped) return members_one_sampler(g, s, iterations, batch, steps, momenta, noise);
-    return GroupedCall{g}.run(steps, momenta, [&](GroupLaunch &) { return train_sampled_run(h0, s, iterations, batch, steps[0], momenta[0], noise); });
+    return GroupedCall{g}.run(steps, momenta, [&](GroupLaunch &) { return train_sampled_run(h0, &s, 1, iterations, &batch, steps[0], momenta[0], noise, nullptr, nullptr); });
 }); }
 
 /* The observed loop (NNT:68-72 / 75-79) of a group: the sampled loops with, behind every step and still under the
@@ -393,44 +393,48 @@ int gnn_mlp_group_train_sampled_observed(gnn_mlp_group_t *g, gnn_sampler_t *s, i
         return members_one_sampler(g, s, iterations, batch, steps, momenta, noise, validation_size, val_loss);
     GroupValidation obs;
     TRY(obs.make(g, iterations, validation_size));
-    TRY(GroupedCall{g}.run(steps, momenta, [&](GroupLaunch &) { return train_sampled_run(h0, s, iterations, batch, steps[0], momenta[0], noise, &obs); }));
+    TRY(GroupedCall{g}.run(steps, momenta, [&](GroupLaunch &) { return train_sampled_run(h0, &s, 1, iterations, &batch, steps[0], momenta[0], noise, &obs, nullptr); }));
     return obs.read(false, val_loss);
 }); }
 
 } // extern "C"
 
-/* One sampler per member.  The loop is train_sampled_impl's on member 0 with K index rings (sampler.hip); an iteration in
+/* One sampler per member.  The loop is train_sampled_run on member 0 with K index rings (sampler.hip); an iteration in
  * which every member's batch has the same size is the two grouped launches, member k reading ring k through the index region
  * (group_kernels.h).  A refill shortens a batch per member (NNT:149-155), so around a refill the sizes may differ: such a
  * MIXED iteration is stepped member after member through the members' own handles, outside the GroupScope -- the lone step by
  * construction.  Nothing is announced for it and every member's look-ahead state is forgotten on both sides of it (bitwise
  * neutral: one forward-only launch when the grouped chain resumes). */
 namespace {
-struct EachMember : SampledEach {
-    gnn_mlp_group *g; GroupLaunch *gl; const double *steps, *momenta;
-    size_t slice_elems = 0;
-    int64_t &mixed; // (the call's: GroupedCall::run hands the members the grouped iterations only)
-    EachMember(GroupedCall &call, GroupLaunch &gl_, const double *steps_, const double *momenta_)
-        : g(call.g), gl(&gl_), steps(steps_), momenta(momenta_), mixed(call.mixed) {}
-    ~EachMember() override { if (gl->idx_lo) region(nullptr, 0); } // (the loop was left by an exception)
+// What both forms of the group's side share: the index region's way into the launches' arguments and out of the members' states.
+// sizes: the per-member sizes the members leave the region with (a sized call's), or null.
+struct MemberRegion : SampledEach {
+    gnn_mlp_group *g; GroupLaunch *gl; const GroupSizes *sizes;
+    MemberRegion(gnn_mlp_group *g_, GroupLaunch *gl_, const GroupSizes *sizes_) : g(g_), gl(gl_), sizes(sizes_) {}
+    ~MemberRegion() override { if (gl->idx_lo) MemberRegion::region(nullptr, 0); } // (the loop was left by an exception)
     void region(const int32_t *lo, size_t slice_bytes) override {
         if (!lo) { // about to be released: no member keeps an address inside it
-            leave_grouped(g, 0, gl->idx_lo, gl->idx_S);
+            leave_grouped(g, 0, gl->idx_lo, gl->idx_S, sizes);
             for (gnn_mlp *h : g->m) h->la.index_region_released();
         }
         gl->idx_lo = reinterpret_cast<const char *>(lo); gl->idx_S = slice_bytes;
-        slice_elems = slice_bytes / sizeof(int32_t);
     }
+};
+struct EachMember : MemberRegion {
+    const double *steps, *momenta;
+    int64_t &mixed; // (the call's: GroupedCall::run hands the members the grouped iterations only)
+    EachMember(GroupedCall &call, GroupLaunch &gl_, const double *steps_, const double *momenta_)
+        : MemberRegion(call.g, &gl_, nullptr), steps(steps_), momenta(momenta_), mixed(call.mixed) {}
     void forget_all() { // member 0's state for everyone (one staging buffer index for all), then forgotten
         for (int k = 0; k < g->K; k++) { g->m[k]->la = g->m[0]->la.rebased(g->arena, g->S, k, gl->idx_lo, gl->idx_S); g->m[k]->la.forget(); }
     }
-    int mixed_step(const int32_t *d_idx0, const int *counts) override {
+    int mixed_step(const int32_t *const *d_idx, const int *counts) override {
         gnn_mlp *h0 = g->m[0];
         h0->grp = nullptr; // (outside the GroupScope; set again below on every path)
         forget_all();
         int rc = GNN_OK;
         for (int k = 0; k < g->K && rc == GNN_OK; k++)
-            rc = step_on_device_indices(g->m[k], d_idx0 + (size_t)k * slice_elems, counts[k], steps[k], momenta[k]);
+            rc = step_on_device_indices(g->m[k], d_idx[k], counts[k], steps[k], momenta[k]);
         forget_all();
         h0->grp = gl;
         mixed++;
@@ -444,19 +448,10 @@ struct EachMember : SampledEach {
  * live row count now and in the announced iteration (GroupLaunch::rows / next_rows, group_kernels.h) -- a refill that shortens
  * one member's batch changes that member's entry, nothing else.  The per-iteration decision is group_sizes.h's. */
 namespace {
-struct SizedMembers : SampledEach {
-    gnn_mlp_group *g; GroupLaunch *gl;
+struct SizedMembers : MemberRegion {
     GroupSizes &track; // member k's sizes of the batches member 0's state names, step by step (the call's: the members leave with them)
-    SizedMembers(GroupedCall &call, GroupLaunch &gl_) : g(call.g), gl(&gl_), track(call.track) { track = g->sizes; }
-    ~SizedMembers() override { if (gl->idx_lo) region(nullptr, 0); } // (the loop was left by an exception)
-    void region(const int32_t *lo, size_t slice_bytes) override {
-        if (!lo) { // about to be released: no member keeps an address inside it
-            leave_grouped(g, 0, gl->idx_lo, gl->idx_S, &track);
-            for (gnn_mlp *h : g->m) h->la.index_region_released();
-        }
-        gl->idx_lo = reinterpret_cast<const char *>(lo); gl->idx_S = slice_bytes;
-    }
-    int mixed_step(const int32_t *, const int *) override { return fail(GNN_ERR_STATE, "a sized group call steps no iteration member after member"); }
+    SizedMembers(GroupedCall &call, GroupLaunch &gl_) : MemberRegion(call.g, &gl_, &call.track), track(call.track) { track = g->sizes; }
+    int mixed_step(const int32_t *const *, const int *) override { return fail(GNN_ERR_STATE, "a sized group call steps no iteration member after member"); }
     bool sized() const override { return true; }
     void step_sizes(const int *rows, const int *next_rows) override {
         const SizedStep s = make_sized_step(g->K, rows, next_rows);
@@ -518,7 +513,7 @@ int train_sampled_members(gnn_mlp_group *g, gnn_sampler_t *const *samplers, int 
     if (val_loss && sized) { TRY(alone.make(g, iterations, validation_size)); obs = &alone; }
     GroupedCall call{g, sized, /* counted */ true};
     TRY(call.run(steps, momenta, [&](GroupLaunch &gl) {
-        auto loop = [&](SampledEach *each) { return train_sampled_run_each(h0, samplers, K, iterations, batches, steps[0], momenta[0], noise, obs, each); };
+        auto loop = [&](SampledEach *each) { return train_sampled_run(h0, samplers, K, iterations, batches, steps[0], momenta[0], noise, obs, each); };
         if (sized) { SizedMembers each(call, gl); return loop(&each); }
         EachMember each(call, gl, steps, momenta);
         return loop(&each);
@@ -641,7 +636,7 @@ int gnn_mlp_group_train_sampled_held_out(gnn_mlp_group_t *g, gnn_sampler_t *cons
         GroupedCall call{g, /* sized */ true, /* counted */ true};
         TRY(call.run(steps, momenta, [&](GroupLaunch &gl) {
             SizedMembers each(call, gl);
-            return train_sampled_run_each(h0, samplers, K, iterations, batches, steps[0], momenta[0], noise, &obs, &each);
+            return train_sampled_run(h0, samplers, K, iterations, batches, steps[0], momenta[0], noise, &obs, &each);
         }));
         // (the loop has waited for the stream behind the readbacks: the ONE synchronisation)
     }

@@ -491,7 +491,7 @@ int upload_dataset_u8(gnn_mlp *h, const uint8_t *pixels, const uint8_t *labels, 
 int train_range_checks(gnn_mlp *h, int64_t first, int B, int n_steps, double step);
 int train_range_steps(gnn_mlp *h, int64_t first, int B, int s, int n_steps, double step, double momentum);
 int train_sampled_checks(gnn_mlp *h, gnn_sampler_t *s, int iterations, int batch, double step, int noise);
-// What the sampled training loop (sampler.hip: train_sampled_impl) calls between the steps it enqueues: after_step(i) when step
+// What the sampled training loop (sampler.hip: train_sampled_run) calls between the steps it enqueues: after_step(i) when step
 // i's launches are on the handle's stream, after_chunk(i_end) when every step of a sampler chunk -- iterations up to i_end,
 // i_end == iterations for the last one -- is.  A status other than GNN_OK ends the loop.
 struct SampledObserver {
@@ -499,25 +499,24 @@ struct SampledObserver {
     virtual int after_chunk(int i_end) { (void)i_end; return GNN_OK; }
     virtual ~SampledObserver() {}
 };
-int train_sampled_run(gnn_mlp *h, gnn_sampler_t *s, int iterations, int batch, double step, double momentum, int noise,
-                      SampledObserver *obs = nullptr);
 // The group's side of the loop with ONE SAMPLER PER MEMBER (group.hip: gnn_mlp_group_train_sampled_each), run on member 0's handle:
 // region(lo, slice_bytes) when the device index region exists (member m's ring at lo + m * slice_bytes) and region(null, 0)
-// just before it is released; mixed_step(d_idx0, counts) steps ONE iteration whose batch sizes counts[m] differ between the
-// members -- member m's indices at d_idx0 + m * slice -- and leaves member 0's handle ready for the next grouped step.
+// just before it is released; mixed_step(d_idx, counts) steps ONE iteration whose batch sizes counts[m] differ between the
+// members -- member m's indices at d_idx[m] -- and leaves member 0's handle ready for the next grouped step.
 // sized() (gnn_mlp_group_train_sampled_sizes): the grouped launches take every member's own row count, so NO iteration is
 // mixed -- the loop calls step_sizes(rows, next_rows) in front of every step with the members' live rows in the iteration it is
 // about to step and in the one it announces (null: none announced), then steps member 0 as ever.
 struct SampledEach {
     virtual void region(const int32_t *lo, size_t slice_bytes) = 0;
-    virtual int mixed_step(const int32_t *d_idx0, const int *counts) = 0;
+    virtual int mixed_step(const int32_t *const *d_idx, const int *counts) = 0;
     virtual bool sized() const { return false; }
     virtual void step_sizes(const int *rows, const int *next_rows) { (void)rows; (void)next_rows; }
     virtual ~SampledEach() {}
 };
-// batches[m]: sampler m's nominal batch size (all equal unless each->sized()); every ring has the slot stride of the largest
-int train_sampled_run_each(gnn_mlp *h, gnn_sampler_t *const *samplers, int n, int iterations, const int *batches, double step,
-                           double momentum, int noise, SampledObserver *obs, SampledEach *each);
+// The loop itself, for n samplers (a lone handle: &s, 1, &batch, each null).  batches[m]: sampler m's nominal batch size (all
+// equal unless each->sized()); every ring has the slot stride of the largest (index_ring.h)
+int train_sampled_run(gnn_mlp *h, gnn_sampler_t *const *samplers, int n, int iterations, const int *batches, double step,
+                      double momentum, int noise, SampledObserver *obs, SampledEach *each);
 // the held-out curve (sampler.hip; keep_best_kernel.h): a handle's snapshot buffer and history for `points` points, the launch for
 // K nets of one shape, the arguments both entry points refuse
 int ensure_keep_best(gnn_mlp *h, int points);

@@ -26,6 +26,7 @@ struct ChunkSchedule {
         return b;
     }
     int end(int c) const { return std::min(iterations, begin(c + 1)); }
+    int length(int c) const { return end(c) - begin(c); }
     int chunks() const { int n = 0; while (begin(n) < iterations) n++; return n; }
 };
 

@@ -2,7 +2,7 @@
 // refillSampler on java.util.Random, and gnn_mlp_train_sampled, the train loop of NNT:60-92 on a resident dataset.
 #include "handle.h"
 #include "java_random.h"
-#include "sample_ring.h"
+#include "index_ring.h"
 
 #include <algorithm>
 
@@ -147,14 +147,102 @@ int gnn::host::train_sampled_checks(gnn_mlp *h, gnn_sampler_t *s, int iterations
 gnn_sampler_t *gnn::host::sampler_copy(const gnn_sampler_t *s) { return new gnn_sampler(*s); }
 void gnn::host::sampler_assign(gnn_sampler_t *dst, const gnn_sampler_t *src) { *dst = *src; }
 
+namespace {
+// The index storage of one call of the loop below: n rings of kIndexRingSlots chunk slots on the host and on the device
+// (index_ring.h: IndexRingLayout says where everything lies, UploadWindow which chunks are where), slice m of ONE pinned and ONE
+// device allocation -- the device one is the index region of group_kernels.h -- and the drawn batch sizes beside them.
+// The host ring is PINNED memory and every upload is followed by an event: the copy is then truly asynchronous (from pageable
+// memory hipMemcpyAsync stages the data before it returns -- in this runtime by waiting for the stream, i.e. for every step
+// queued so far: the GPU idled at each chunk boundary, and the slot's safety rested on that behaviour), and a host slot goes
+// back to the samplers only when its event has completed.
+struct DeviceIndexRing {
+    // an iteration on the device: member 0's indices, every member's batch size, whether those sizes agree
+    struct Iteration {
+        const int32_t *idx0 = nullptr; int counts[GROUP_MAX]; bool same = true;
+        explicit operator bool() const { return idx0 != nullptr; }
+    };
+    const IndexRingLayout lay; UploadWindow win; hipStream_t stream; SampleRing &sr;
+    int32_t *host = nullptr; hipEvent_t ev[kIndexRingSlots] = {};
+    std::vector<int> cnt, dcnt; // the batch sizes as drawn (the samplers write them) / of the chunks on the device
+    DevScratch dev;
+    DeviceIndexRing(const IndexRingLayout &lay_, const ChunkSchedule &sched, hipStream_t stream_, SampleRing &sr_)
+        : lay(lay_), win{sched}, stream(stream_), sr(sr_), cnt(lay_.total_counts()), dcnt(lay_.total_counts(), 0) {}
+    ~DeviceIndexRing() { if (host) (void)hipHostFree(host); for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+    int alloc() {
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&host), lay.total_elems() * sizeof(int32_t), hipHostMallocDefault));
+        for (hipEvent_t &e : ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        return dev.alloc(lay.total_elems() * sizeof(int32_t));
+    }
+    // -- the workers' side: where member m's draw of iteration `at` of chunk c goes
+    int32_t *host_slot(int m, int c, int at) { return host + lay.index_at(m, c, at); }
+    int *host_counts(int m, int c, int at) { return &cnt[lay.count_at(m, c, at)]; }
+    // -- the device side (indices(0, 0, 0): the region's first byte)
+    const int32_t *indices(int m, int c, int at) const { return dev.as<int32_t>() + lay.index_at(m, c, at); }
+    void counts(int c, int at, int *out) const { for (int m = 0; m < lay.members; m++) out[m] = dcnt[lay.count_at(m, c, at)]; }
+    Iteration iteration(RingPos p) const {
+        Iteration it;
+        it.idx0 = indices(0, p.chunk, p.at);
+        counts(p.chunk, p.at, it.counts);
+        for (int m = 1; m < lay.members; m++) it.same = it.same && it.counts[m] == it.counts[0];
+        return it;
+    }
+    // Chunk c's draws go to the device ring: one copy per member, one event behind them.  The batch sizes are copied out of the
+    // host ring at once (the host slot is the samplers' again before the chunk's steps run); the indices stay in the pinned slot
+    // until the copy has run.
+    int upload(int c) {
+        const int len = win.sched.length(c);
+        for (int m = 0; m < lay.members; m++) {
+            const size_t i0 = lay.index_at(m, c, 0), i1 = lay.index_at(m, c, len), c0 = lay.count_at(m, c, 0), c1 = lay.count_at(m, c, len);
+            std::copy(cnt.begin() + c0, cnt.begin() + c1, dcnt.begin() + c0);
+            HIP_TRY(hipMemcpyAsync(dev.as<int32_t>() + i0, host + i0, (i1 - i0) * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+        }
+        HIP_TRY(hipEventRecord(ev[lay.slot(c)], stream));
+        win.uploaded_chunk(c);
+        return GNN_OK;
+    }
+    // hands finished uploads' host slots back to the samplers: those whose event has completed -- waiting for the OLDEST one when `wait`
+    // (an upload sits in front of the steps of the chunk BEFORE its own, so by the time the samplers need the slot,
+    //  kIndexRingSlots chunks later, the copy ran long ago: the wait does not stall)
+    int release(bool wait) {
+        hipError_t q = hipSuccess; // (the last answer: the error, when the window reports one)
+        const bool ok = win.release(wait, [&](int c, bool block) {
+            q = block ? hipEventSynchronize(ev[lay.slot(c)]) : hipEventQuery(ev[lay.slot(c)]);
+            return q == hipSuccess ? UploadPoll::done : q == hipErrorNotReady ? UploadPoll::not_ready : UploadPoll::error;
+        }, [&](int upto) { sr.release(upto); });
+        return ok ? GNN_OK : fail(GNN_ERR_HIP, std::string("upload event: ") + hipGetErrorString(q));
+    }
+    // Chunk c on the device, waiting for its draws if need be -- and chunk c + 1 IN FRONT OF chunk c's steps when the samplers
+    // have it (which they have: they run kIndexRingSlots chunks ahead; no waiting for it): the last step of a chunk then knows its
+    // successor like every other step, and the chain of two-launch steps runs through the chunk boundary -- an upload in stream
+    // order at the boundary left the GPU idle for the copy and restarted the chain with a forward-only launch, ~1 us per step
+    // over a run.
+    int stage(int c) {
+        TRY(release(false));
+        if (win.next(c)) {
+            // (the samplers may be waiting for a host slot whose upload is still in flight: hand slots back while waiting for them)
+            while (!sr.ready(c)) {
+                TRY(release(win.full()));
+                if (sr.wait_ready(c, 200)) break;
+            }
+            std::string msg;
+            if (const int src = sr.error(&msg)) return fail(src, msg);
+            TRY(upload(c));
+        }
+        if (c + 1 < sr.chunks() && sr.ready(c + 1) && sr.error() == GNN_OK) TRY(upload(c + 1));
+        return GNN_OK;
+    }
+};
+} // namespace
+
+// The loop NNT:60-92 on a resident dataset, for n samplers (lone callers: one).
 // `obs` (handle.h: SampledObserver) is called behind every step and behind every sampler chunk, on the calling thread, with the
 // handle's stream holding everything enqueued so far: the observed loops below and the group's (group.hip) are this loop + one.
-// n samplers (n > 1: `each`, a group call with one sampler per member on member 0's handle): sampler m draws batches of
-// batches[m] into ring m, and an iteration whose n batch sizes differ is handed to each->mixed_step instead of being stepped
-// here -- unless each->sized(): the grouped launches then take every member's own size (each->step_sizes) and every iteration is
-// stepped here.  Unless sized, the n nominal sizes are equal.
-static int train_sampled_impl(gnn_mlp_t *h, gnn_sampler_t *const *samplers, int n, int iterations, const int *batches, double step,
-                              double momentum, int noise, SampledObserver *obs, SampledEach *each) {
+// n > 1: `each`, a group call with one sampler per member on member 0's handle.  Sampler m draws batches of batches[m] into
+// ring m, and an iteration whose n batch sizes differ is handed to each->mixed_step instead of being stepped here -- unless
+// each->sized(): the grouped launches then take every member's own size (each->step_sizes) and every iteration is stepped here.
+// Unless sized, the n nominal sizes are equal.
+int gnn::host::train_sampled_run(gnn_mlp *h, gnn_sampler_t *const *samplers, int n, int iterations, const int *batches, double step,
+                                 double momentum, int noise, SampledObserver *obs, SampledEach *each) {
     TRY(check_handle(h));
     if (n < 1 || n > GROUP_MAX || (n > 1 && !each)) return fail(GNN_ERR_BAD_ARG, "bad sampler count");
     const bool sized = each && each->sized();
@@ -170,164 +258,54 @@ static int train_sampled_impl(gnn_mlp_t *h, gnn_sampler_t *const *samplers, int 
     // chunk, while this thread uploads finished chunks and enqueues their steps.  The first chunks are short
     // (16, 32, 64, 128, then 256 iterations): nothing runs on the GPU until the first one is sampled, and a 256-batch
     // first chunk kept it idle for 2.5 ms (0.85 us per step of a 3 000-step call).
-    // Index storage is a RING of kRing chunk slots on the host and on the device, whatever the run length (NNT:62 runs
-    // 500 000 iterations): the sampler waits for a free host slot; a device slot is rewritten by a copy that is enqueued on
-    // the handle's stream behind the steps that read it.
-    // With n samplers there are n such rings, slice m of ONE pinned and ONE device allocation (the device one is the index
-    // region of group_kernels.h), drawn by min(n, 8) worker threads (sample_ring.h: a grouped step of 8 nets takes 37 us, eight
-    // samplers on one thread 80).  The chunks are then shortened so that the n rings together stay within kPinnedBound.
-    static constexpr int kRing = 4, kChunk = 256;
-    static constexpr size_t kPinnedBound = (size_t)64 << 20;
-    int kc = kChunk;
-    if (n > 1) while (kc > 1 && (size_t)n * kRing * kc * batch * sizeof(int32_t) > kPinnedBound) kc /= 2;
-    const ChunkSchedule sched{iterations, kc};
-    auto chunk_begin = [&](int c) { return sched.begin(c); };
-    auto chunk_end = [&](int c) { return sched.end(c); };
-    const int n_chunks = sched.chunks();
-    const size_t slot_elems = (size_t)kc * batch;
-    const size_t slice_elems = (slot_elems * kRing + 63) / 64 * 64; // (a slice starts on a 256-byte boundary)
-    const size_t cnt_slice = (size_t)kc * kRing;
-    // The host ring is PINNED memory and every upload is followed by an event: the copy is then truly asynchronous (from pageable
-    // memory hipMemcpyAsync stages the data before it returns -- in this runtime by waiting for the stream, i.e. for every step
-    // queued so far: the GPU idled at each chunk boundary, and the slot's safety rested on that behaviour), and a host slot goes
-    // back to the sampler only when its event has completed.
-    struct PinnedRing {
-        int32_t *p = nullptr; hipEvent_t ev[kRing] = {};
-        ~PinnedRing() { if (p) (void)hipHostFree(p); for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
-    } ring;
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&ring.p), slice_elems * n * sizeof(int32_t), hipHostMallocDefault));
-    for (int i = 0; i < kRing; i++) HIP_TRY(hipEventCreateWithFlags(&ring.ev[i], hipEventDisableTiming));
-    int32_t *const idx = ring.p;
-    std::vector<int> cnt(cnt_slice * n);
-    std::vector<int> dcnt(cnt_slice * n, 0); // the batch sizes of the chunks on the device (the host ring is the sampler's again by then)
-    DevScratch dbuf;
-    TRY(dbuf.alloc(slice_elems * n * sizeof(int32_t)));
-    int32_t *d_idx = dbuf.as<int32_t>();
-    SampleRing sr(n, kRing, n_chunks);
+    // Index storage is a RING of chunk slots on the host and on the device, whatever the run length (NNT:62 runs 500 000
+    // iterations): the sampler waits for a free host slot; a device slot is rewritten by a copy that is enqueued on the handle's
+    // stream behind the steps that read it.  With n samplers there are n such rings, drawn by min(n, 8) worker threads
+    // (sample_ring.h: a grouped step of 8 nets takes 37 us, eight samplers on one thread 80); the chunks are then shortened so
+    // that the n rings together stay within the pinned bound (index_ring.h).
+    const IndexRingLayout lay{n, IndexRingLayout::chunk_cap(n, batch), batch};
+    const ChunkSchedule sched{iterations, lay.cap};
+    SampleRing sr(n, lay.slots, sched.chunks());
+    DeviceIndexRing ring(lay, sched, h->stream, sr);
+    TRY(ring.alloc());
     // (declared behind everything the workers write: they are joined first on every exit path)
     SampleWorkers workers(sr, SampleWorkers::threads_for(n), [&](int m, int c, std::string *msg) -> int {
         int rc = GNN_OK;
-        const int i0 = chunk_begin(c), i1 = chunk_end(c);
-        int32_t *slot = idx + (size_t)m * slice_elems + (size_t)(c % kRing) * slot_elems;
-        int *scnt = cnt.data() + (size_t)m * cnt_slice + (size_t)(c % kRing) * kc;
-        for (int i = i0; i < i1 && rc == GNN_OK; i++) rc = gnn_sampler_sample(samplers[m], batches[m], slot + (size_t)(i - i0) * batch, &scnt[i - i0]);
+        for (int at = 0, len = sched.length(c); at < len && rc == GNN_OK; at++)
+            rc = gnn_sampler_sample(samplers[m], batches[m], ring.host_slot(m, c, at), ring.host_counts(m, c, at));
         if (rc != GNN_OK) *msg = gnn_mlp_last_error();
         return rc;
     });
-    if (each) each->region(d_idx, slice_elems * sizeof(int32_t));
+    if (each) each->region(ring.indices(0, 0, 0), lay.slice_elems() * sizeof(int32_t));
     int rc = GNN_OK;
-    // Chunk c + 1's draws go to the device ring BEFORE chunk c's steps are enqueued (when the sampler has them, which it has:
-    // it runs kRing chunks ahead): the last step of a chunk then knows its successor like every other step, and the chain of
-    // two-launch steps runs through the chunk boundary -- an upload in stream order at the boundary left the GPU idle for
-    // the copy and restarted the chain with a forward-only launch, ~1 us per step over a run.
-    int uploaded = 0; // chunks whose draws are on the device (or in flight in front of every launch that reads them)
-    int released = 0; // chunks whose HOST slot is the sampler's again (their upload's event has completed)
-    auto upload = [&](int c) -> int { // (every member's part: one copy per ring, one event behind them)
-        const int j0 = chunk_begin(c), j1 = chunk_end(c);
-        hipError_t e = hipSuccess;
-        for (int m = 0; m < n && e == hipSuccess; m++) {
-            const size_t so = (size_t)m * slice_elems + (size_t)(c % kRing) * slot_elems, co = (size_t)m * cnt_slice + (size_t)(c % kRing) * kc;
-            // (the counts are copied out of the ring at once; the indices stay in the pinned slot until the copy has run)
-            std::copy(cnt.begin() + co, cnt.begin() + co + (j1 - j0), dcnt.begin() + co);
-            e = hipMemcpyAsync(d_idx + so, idx + so, (size_t)(j1 - j0) * batch * sizeof(int32_t), hipMemcpyHostToDevice, h->stream);
-        }
-        if (e == hipSuccess) e = hipEventRecord(ring.ev[c % kRing], h->stream);
-        if (e != hipSuccess) return fail(GNN_ERR_HIP, std::string("hipMemcpyAsync: ") + hipGetErrorString(e));
-        uploaded = c + 1;
-        return GNN_OK;
-    };
-    // hands finished uploads' host slots back to the sampler: those whose event has completed -- all of them when `wait`
-    // (an upload sits in front of the steps of the chunk BEFORE its own, so by the time the sampler needs the slot,
-    //  kRing chunks later, the copy ran long ago: the wait does not stall)
-    auto release = [&](bool wait) -> int {
-        int r = released;
-        while (r < uploaded) {
-            const hipError_t q = (wait && r == released) ? hipEventSynchronize(ring.ev[r % kRing]) : hipEventQuery(ring.ev[r % kRing]); // (wait: for the OLDEST one)
-            if (q == hipErrorNotReady) break;
-            if (q != hipSuccess) return fail(GNN_ERR_HIP, std::string("upload event: ") + hipGetErrorString(q));
-            r++;
-        }
-        if (r != released) { released = r; sr.release(r); }
-        return GNN_OK;
-    };
-    // the n batch sizes of the iteration at `at` of chunk slot `slot` (on the device): member 0's when they agree, else -1
-    auto common_count = [&](int slot, int at) {
-        const int c0 = dcnt[(size_t)slot * kc + at];
-        for (int m = 1; m < n; m++) if (dcnt[(size_t)m * cnt_slice + (size_t)slot * kc + at] != c0) return -1;
-        return c0;
-    };
-    // every member's batch size of that iteration
-    auto member_counts = [&](int slot, int at, int *out) {
-        for (int m = 0; m < n; m++) out[m] = dcnt[(size_t)m * cnt_slice + (size_t)slot * kc + at];
-    };
-    int member_cnt[GROUP_MAX], next_cnt[GROUP_MAX];
-    for (int c = 0; c < n_chunks && rc == GNN_OK; c++) {
-        rc = release(false);
-        if (rc != GNN_OK) break;
-        if (uploaded <= c) {
-            // (the sampler may be waiting for a host slot whose upload is still in flight: hand slots back while waiting for it)
-            while (!sr.ready(c)) {
-                rc = release(uploaded - released >= kRing); // every slot taken and none released: wait for the oldest upload
-                if (rc != GNN_OK || sr.wait_ready(c, 200)) break;
-            }
-            if (rc != GNN_OK) break;
-            std::string msg;
-            if (const int src = sr.error(&msg)) { rc = fail(src, msg); break; }
-            rc = upload(c);
-            if (rc != GNN_OK) break;
-        }
-        if (c + 1 < n_chunks) { // the successor too, if it is drawn already (no waiting for it)
-            if (sr.ready(c + 1) && sr.error() == GNN_OK) { rc = upload(c + 1); if (rc != GNN_OK) break; }
-        }
-        const int i0 = chunk_begin(c), i1 = chunk_end(c);
-        const int slot = c % kRing, slot_n = (c + 1) % kRing;
-        const size_t so = (size_t)slot * slot_elems, sn = (size_t)slot_n * slot_elems;
-        for (int i = i0; i < i1 && rc == GNN_OK; i++) {
-            if (sized) { // every member with its own size, in the two grouped launches: the sizes travel beside the announcement
-                member_counts(slot, i - i0, member_cnt);
-                const int32_t *next_idx = nullptr;
-                if (h->chain && i + 1 < i1) { next_idx = d_idx + so + (size_t)(i + 1 - i0) * batch; member_counts(slot, i + 1 - i0, next_cnt); }
-                else if (h->chain && uploaded > c + 1) { next_idx = d_idx + sn; member_counts(slot_n, 0, next_cnt); }
-                each->step_sizes(member_cnt, next_idx ? next_cnt : nullptr);
-                if (next_idx) h->la.announce(NextBatch{h->DX, next_idx, next_cnt[0]});
-                rc = step_on_device_indices(h, d_idx + so + (size_t)(i - i0) * batch, member_cnt[0], step, momentum);
-                if (rc == GNN_OK && obs) rc = obs->after_step(i);
-                continue;
-            }
-            const int B = common_count(slot, i - i0);
-            if (B < 0) { // the members' batches differ in size (a refill shortened some): member after member, nothing announced
-                member_counts(slot, i - i0, member_cnt);
-                rc = each->mixed_step(d_idx + so + (size_t)(i - i0) * batch, member_cnt);
+    for (int c = 0; c < sr.chunks() && rc == GNN_OK; c++) {
+        rc = ring.stage(c);
+        const int i0 = sched.begin(c), len = sched.length(c);
+        for (int at = 0; at < len && rc == GNN_OK; at++) {
+            const DeviceIndexRing::Iteration it = ring.iteration(RingPos{c, at});
+            const RingPos next = h->chain ? ring.win.successor(c, at) : RingPos{};
+            const DeviceIndexRing::Iteration nx = next ? ring.iteration(next) : DeviceIndexRing::Iteration{}; // the one to announce, if it is on the device already
+            if (!sized && !it.same) { // the members' batches differ in size (a refill shortened some): member after member, nothing announced
+                const int32_t *idx[GROUP_MAX];
+                for (int m = 0; m < n; m++) idx[m] = ring.indices(m, c, at);
+                rc = each->mixed_step(idx, it.counts);
             } else {
-                if (h->chain && i + 1 < i1) { // the next draw of this chunk is already on the device
-                    const int Bn = common_count(slot, i + 1 - i0);
-                    if (Bn >= 0) h->la.announce(NextBatch{h->DX, d_idx + so + (size_t)(i + 1 - i0) * batch, Bn});
-                } else if (h->chain && uploaded > c + 1) { // ... and so is the first draw of the next chunk
-                    const int Bn = common_count(slot_n, 0);
-                    if (Bn >= 0) h->la.announce(NextBatch{h->DX, d_idx + sn, Bn});
-                }
-                rc = step_on_device_indices(h, d_idx + so + (size_t)(i - i0) * batch, B, step, momentum);
+                // (sized: every member with its own size, in the two grouped launches -- the sizes travel beside the announcement)
+                if (sized) each->step_sizes(it.counts, nx ? nx.counts : nullptr);
+                if (nx && (sized || nx.same)) h->la.announce(NextBatch{h->DX, nx.idx0, nx.counts[0]});
+                rc = step_on_device_indices(h, it.idx0, it.counts[0], step, momentum);
             }
             // (a validation pass reads the weights the step has just written; it touches neither the slabs the step's tile
             //  kernel made for the next batch nor the staged rows, so the chain of two-launch steps runs on behind it)
-            if (rc == GNN_OK && obs) rc = obs->after_step(i);
+            if (rc == GNN_OK && obs) rc = obs->after_step(i0 + at);
         }
-        if (rc == GNN_OK && obs) rc = obs->after_chunk(i1);
+        if (rc == GNN_OK && obs) rc = obs->after_chunk(i0 + len);
     }
     // (on an early exit the sampler stops after the chunk it is drawing: its state stays well defined)
     (void)hipStreamSynchronize(h->stream); // the device ring is released below
-    h->la.rows_renamed(); // (they may name rows through d_idx)
+    h->la.rows_renamed(); // (they may name rows through the device ring)
     if (each) each->region(nullptr, 0);
     return rc;
-}
-
-int gnn::host::train_sampled_run(gnn_mlp *h, gnn_sampler_t *s, int iterations, int batch, double step, double momentum, int noise,
-                                 SampledObserver *obs) {
-    return train_sampled_impl(h, &s, 1, iterations, &batch, step, momentum, noise, obs, nullptr);
-}
-int gnn::host::train_sampled_run_each(gnn_mlp *h, gnn_sampler_t *const *samplers, int n, int iterations, const int *batches, double step,
-                                      double momentum, int noise, SampledObserver *obs, SampledEach *each) {
-    return train_sampled_impl(h, samplers, n, iterations, batches, step, momentum, noise, obs, each);
 }
 
 // ---- the held-out curve and the best weights (keep_best_kernel.h) --------------------------------------------------------------
@@ -426,7 +404,7 @@ int gnn_mlp_train_sampled_held_out(gnn_mlp_t *h, gnn_sampler_t *s, int iteration
     obs.want_weights = best_weights != nullptr;
     obs.res.assign(2 * (size_t)P, 0);
     if (best_weights) obs.w.assign((size_t)h->n_pad, 0.f);
-    TRY(train_sampled_impl(h, &s, 1, iterations, &batch, step, momentum, noise, &obs, nullptr));
+    TRY(train_sampled_run(h, &s, 1, iterations, &batch, step, momentum, noise, &obs, nullptr));
     // (the loop has waited for the stream behind the readbacks: the ONE synchronisation)
     static_assert(sizeof(unsigned long long) == sizeof(double), "one buffer for counters and sums");
     for (int p = 0; p < P; p++) {
@@ -460,7 +438,7 @@ extern "C" {
 
 int gnn_mlp_train_sampled(gnn_mlp_t *h, gnn_sampler_t *s, int iterations, int batch, double step, double momentum,
                           int noise) { return guarded([&]() -> int {
-    return train_sampled_impl(h, &s, 1, iterations, &batch, step, momentum, noise, nullptr, nullptr);
+    return train_sampled_run(h, &s, 1, iterations, &batch, step, momentum, noise, nullptr, nullptr);
 }); }
 
 int gnn_mlp_train_sampled_observed(gnn_mlp_t *h, gnn_sampler_t *s, int iterations, int batch, double step, double momentum,
@@ -477,13 +455,13 @@ int gnn_mlp_train_sampled_observed(gnn_mlp_t *h, gnn_sampler_t *s, int iteration
     const bool rows_form = eval_block_rows(h, validation_size) >= validation_size && (int64_t)iterations * stride * 4 <= (1ll << 30);
     if (rows_form) TRY(drows.alloc(sizeof(float) * (size_t)iterations * (size_t)stride));
     LoneValidation obs(h, validation_size, dv.as<double>(), rows_form ? drows.as<float>() : nullptr, stride);
-    TRY(train_sampled_impl(h, &s, 1, iterations, &batch, step, momentum, noise, &obs, nullptr));
+    TRY(train_sampled_run(h, &s, 1, iterations, &batch, step, momentum, noise, &obs, nullptr));
     if (rows_form) {
         hipLaunchKernelGGL(sum_rows_kernel, dim3(iterations), dim3(256), 0, h->stream, RowSumParams{drows.as<float>(), stride, validation_size, dv.as<double>()});
         TRY_LAUNCHES(h);
         HIP_TRY(hipStreamSynchronize(h->stream));
     }
-    // (train_sampled_impl has waited for the stream: every sum is in place)
+    // (train_sampled_run has waited for the stream: every sum is in place)
     HIP_TRY(hipMemcpy(val_loss, dv.p, sizeof(double) * (size_t)iterations, hipMemcpyDeviceToHost));
     for (int i = 0; i < iterations; i++) val_loss[i] /= (double)validation_size; // NNT:112
     return GNN_OK;

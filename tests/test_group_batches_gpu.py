@@ -24,6 +24,9 @@ Bn = [784, 100, 50, 10]       # prebuilt instances
 SMALL = [65, 20, 12, 5]       # runtime-shape instances, one ragged 4-row block
 OFF_PATH = [784, 1024, 1024, 1024, 10]
 CHAIN_SEED = 18               # tests/chain_cases.py: 890-166-78-15, a ragged input width (13 slabs and 58 inputs), f32 and bf16 forms
+# tests/group_batch_cases.py's, and the samplers of tests/test_group_samplers_cpu.py's F5 drawing one size per member: 260
+# iterations, five sampler chunks of the loop, a batch shortened for one member only in every one of them
+FIXTURES = dict(bc.FIXTURES, F5=(fx.FIXTURES["F5"][0], list(fx.F5_SIZES), fx.FIXTURES["F5"][2], fx.FIXTURES["F5"][3], [1, 2, 3]))
 
 
 def _lone(gnn, monkeypatch, kind, dims, seed, dtype, max_batch, inner=None):
@@ -66,7 +69,7 @@ def _lone_observed(lone, s, n, batch, step, mom, V):
 
 def _one_rule(gnn, monkeypatch, name, kind, dims, dtype, calls=None, steps=None, moms=None, max_batch=None, inner=None, w_scale=None,
               expect_grouped=True):
-    N, batches, iters, sseeds, wseeds = bc.FIXTURES[name]
+    N, batches, iters, sseeds, wseeds = FIXTURES[name]
     calls = [iters] if calls is None else calls
     K = len(batches)
     max_batch = max(batches) if max_batch is None else max_batch
@@ -127,6 +130,11 @@ def test_two_chunks_beside_one(gnn, monkeypatch, net, dtype):
 # 4 -- the whole GroupArgs arrays
 def test_sixteen_members_batches_1_to_16(gnn, monkeypatch):
     _one_rule(gnn, monkeypatch, "SIXTEEN", "sce", SMALL, 0)
+
+
+# 4b -- member offsets across the loop's sampler chunks (they begin at iterations 0, 16, 48, 112, 240) and the wrap of its ring of four slots
+def test_across_chunk_boundaries_and_the_rings_wrap(gnn, monkeypatch):
+    _one_rule(gnn, monkeypatch, "F5", "sce", SMALL, 0)  # (asserts sampled_each_iterations == (260, 0): every iteration grouped)
 
 
 # 5 -- the observed form

@@ -12,7 +12,12 @@ FIXTURES = {
     "F2": (40, 12, 14, [1, 2, 3], None),
     "F3": (50, 16, 12, list(range(1, 17)), None),
     "F4": (203, 48, 13, [1, 1, 7], [0, 20, 45]),
+    # F1 run on into the fifth sampler chunk of the training loop (csrc/sample_ring.h: the chunks begin at iterations 0, 16, 48,
+    # 112, 240), which reuses slot 0 of the loop's ring of four chunk slots; its properties are computed below, not tabulated
+    "F5": (203, 48, 260, [1, 1, 7], None),
 }
+F5_SIZES = (48, 40, 24)  # the batch sizes F5's samplers draw with in tests/test_group_batches_gpu.py (one size per member)
+RING_SLOTS = 4
 # iterations (0-based) whose batch sizes differ between the members; and those with a shortened batch of ONE size for all
 DIFFER = {"F1": [4, 12], "F2": [3, 6, 13], "F3": [3, 6, 9], "F4": [3, 4, 7, 8, 11, 12]}
 AGREE_SHORT = {"F1": [8], "F2": [], "F3": [], "F4": []}
@@ -43,7 +48,53 @@ def predict(oracle_mod, name, iterations=None, skip=0):
     return (sizes.shape[0] - len(mixed), len(mixed)), mixed
 
 
-@pytest.mark.parametrize("name", sorted(FIXTURES))
+def chunk_starts(iterations, cap=256):
+    """First iterations of the training loop's sampler chunks: 16, 32, 64, .. iterations doubling up to `cap`, then `cap` each."""
+    starts, begin, size = [], 0, min(16, cap)
+    while begin < iterations:
+        starts.append(begin)
+        begin, size = begin + size, min(cap, size * 2)
+    return starts
+
+
+def chunk_of(starts, i):
+    return max(c for c, s in enumerate(starts) if s <= i)
+
+
+def test_f5_crosses_four_chunk_boundaries_and_the_rings_wrap(oracle_mod):
+    """Every chunk of F5 holds an iteration whose batch sizes differ between the members, the first iteration of chunk 1 is one
+    (its predecessor meets a mixed successor across a chunk boundary), and chunk 4 reuses the ring slot of chunk 0."""
+    N, batch, iters, seeds, _ = FIXTURES["F5"]
+    starts = chunk_starts(iters)
+    assert starts == [0, 16, 48, 112, 240] and len(starts) == RING_SLOTS + 1  # (the schedule of csrc/sample_ring.h, cap 256)
+    sizes = batch_sizes(oracle_mod, "F5")
+    assert np.array_equal(sizes[:FIXTURES["F1"][2]], batch_sizes(oracle_mod, "F1"))  # F1 run on
+    (grouped, mixed_n), mixed = predict(oracle_mod, "F5")
+    per_chunk = [sum(1 for i in mixed if chunk_of(starts, i) == c) for c in range(len(starts))]
+    print("F5: %d iterations whose sizes differ, per chunk %s, smallest batch %d" % (mixed_n, per_chunk, sizes.min()))
+    assert all(n >= 1 for n in per_chunk)
+    assert starts[1] in mixed
+    assert sizes.min() >= 43
+    assert grouped > 0 and grouped + mixed_n == iters
+
+
+def test_f5_samplers_with_a_size_per_member_meet_a_refill_in_every_chunk(oracle_mod):
+    """F5's samplers drawing F5_SIZES: every chunk contains a batch that a refill shortened for ONE member only."""
+    N, _, iters, seeds, _ = FIXTURES["F5"]
+    starts = chunk_starts(iters)
+    sizes = np.empty((iters, len(seeds)), dtype=np.int64)
+    for k, (seed, b) in enumerate(zip(seeds, F5_SIZES)):
+        s = oracle_mod.Sampler(N, seed=seed)
+        sizes[:, k] = [len(s.sample(b)) for _ in range(iters)]
+    assert max(F5_SIZES) < N and (sizes <= np.array(F5_SIZES)).all() and sizes.min() >= 1
+    short = sizes != np.array(F5_SIZES)
+    one_only = [i for i in range(iters) if short[i].sum() == 1]
+    per_chunk = [sum(1 for i in one_only if chunk_of(starts, i) == c) for c in range(len(starts))]
+    print("F5 with sizes %s: batches shortened for one member only, per chunk %s" % (F5_SIZES, per_chunk))
+    assert all(n >= 1 for n in per_chunk)
+
+
+@pytest.mark.parametrize("name", sorted(DIFFER))
 def test_fixture_has_the_iterations_the_gpu_tests_need(oracle_mod, name):
     N, batch, iters, seeds, _ = FIXTURES[name]
     sizes = batch_sizes(oracle_mod, name)

@@ -137,6 +137,17 @@ def test_samplers_advanced_before_the_call(gnn, monkeypatch, oracle_mod):
     _one_rule(gnn, monkeypatch, oracle_mod, "F4", "sce", SMALL, 0, [1, 2, 3])
 
 
+# 5b
+@pytest.mark.parametrize("calls", [[260], [17, 243]], ids=["one-call", "cut-at-17"])
+def test_across_chunk_boundaries_and_the_rings_wrap(gnn, monkeypatch, oracle_mod, calls):
+    """F5: 260 iterations are five sampler chunks of the loop (they begin at 0, 16, 48, 112, 240), the fifth in ring slot 0 again;
+    every chunk holds iterations stepped member after member, iteration 16 -- the first of chunk 1 -- among them
+    (tests/test_group_samplers_cpu.py).  Cut at 17, the second call's chunks lie elsewhere in the samplers' sequences."""
+    assert sum(calls) == fx.FIXTURES["F5"][2]
+    said = _one_rule(gnn, monkeypatch, oracle_mod, "F5", "sce", SMALL, 0, [1, 2, 3], calls=calls)
+    assert all(grouped > 0 and mixed > 0 for grouped, mixed in said)
+
+
 # 6
 def test_mixed_with_the_other_group_calls(gnn, monkeypatch, oracle_mod):
     N, batch, _, sseeds, _ = fx.FIXTURES["F2"]
