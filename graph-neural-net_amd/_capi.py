@@ -115,6 +115,12 @@ SYMBOLS = [
     ("gnn_mlp_group_confusion_set_range", C.c_int, [_H, C.c_int, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _ip]),
     ("gnn_mlp_group_train_sampled_held_out", C.c_int, [_H, C.POINTER(_H), C.c_int, _ip, _dp, _dp, C.c_int, C.c_int, C.c_int64, C.c_int,
                                                        C.POINTER(C.c_int64), _dp, C.POINTER(C.c_int64), _ip, _dp]),
+    ("gnn_mlp_get_targets_range", C.c_int, [_H, C.c_int, C.c_int64, C.c_int64, _dp]),
+    ("gnn_mlp_set_targets_range", C.c_int, [_H, C.c_int, C.c_int64, C.c_int64, _dp]),
+    ("gnn_mlp_group_set_targets_range", C.c_int, [_H, C.c_int, C.c_int64, C.c_int64, _dp]),
+    ("gnn_mlp_propagate_set_range", C.c_int, [_H, C.c_int, C.c_int64, C.c_int64, _dp]),
+    ("gnn_mlp_distill_range", C.c_int, [_H, _H, C.c_int64, C.c_int64, C.c_double]),
+    ("gnn_mlp_group_distill_range", C.c_int, [_H, _H, C.c_int64, C.c_int64, C.c_double]),
     ("gnn_mlp_forget_lookahead", C.c_int, [_H]),
     ("gnn_mlp_advance_time", C.c_int, [_H, C.c_int]),
     ("gnn_mlp_recover_stream", C.c_int, [_H]),

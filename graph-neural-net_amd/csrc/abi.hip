@@ -432,7 +432,7 @@ static int alloc_dataset(gnn_mlp *h, int64_t N, int set) { return guarded([&]() 
     return GNN_OK;
 }); }
 
-static const char *kMemberData = "a member of a group trains on the group's dataset (gnn_mlp_group_upload_dataset)";
+static const char *kMemberData = member_set_message(GNN_SET_TRAIN);
 int gnn_mlp_upload_dataset(gnn_mlp_t *h, const double *X, const double *Y, int64_t N) { return guarded([&]() -> int {
     TRY(check_handle(h));
     if (h->group) return fail(GNN_ERR_STATE, kMemberData);
@@ -443,7 +443,7 @@ int gnn_mlp_upload_dataset_u8(gnn_mlp_t *h, const uint8_t *pixels, const uint8_t
     if (h->group) return fail(GNN_ERR_STATE, kMemberData);
     return upload_dataset_u8(h, pixels, labels, N);
 }); }
-static const char *kMemberHeld = "a member of a group sees the group's held-out set (gnn_mlp_group_upload_held_out)";
+static const char *kMemberHeld = member_set_message(GNN_SET_HELD_OUT);
 int gnn_mlp_upload_held_out(gnn_mlp_t *h, const double *X, const double *Y, int64_t N) { return guarded([&]() -> int {
     TRY(check_handle(h, false)); // (a pending host-batch update stays pending: the upload reads and writes nothing of it)
     if (h->group) return fail(GNN_ERR_STATE, kMemberHeld);

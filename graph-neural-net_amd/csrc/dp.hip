@@ -316,6 +316,7 @@ int gnn_mlp_dp_create(const int32_t *dims, int n_dims, int out_kind, int inner_a
         // (sized for the whole batch, not for a shard: propagate / loss / argmax on a replica take any batch the handle takes)
         const int rc = gnn_mlp_create(dims, n_dims, out_kind, inner_act, last_act, loss, seed, dtype, devices[r], max_batch, &h);
         if (rc != GNN_OK) return cleanup(rc);
+        h->dp_replica = true;
         d->rep.push_back(h);
     }
     if (reducer == GNN_REDUCE_RCCL) {

@@ -13,6 +13,7 @@
 // here too: the forward kernel's LOSS_ONLY form into a row of the curve matrix, and group_curve_sum_kernel over that matrix.
 #include "handle.h"
 #include "confusion_kernel.h"
+#include "distill_kernel.h"
 
 #include <algorithm>
 #include <memory>
@@ -92,6 +93,7 @@ struct EvalOut { // device results of one call
     float *mean; int32_t *ens_label;                       // [n][d_out], [n] or null
     unsigned long long *confusion = nullptr;               // [K + 1][d_out][d_out] or null: the members', then the ensemble's (needs ens_label)
     int32_t *member_labels = nullptr;                      // [K][n] or null (with confusion only)
+    float *blend_y = nullptr; float keep = 0.f;            // gnn_mlp_group_distill_range: row `first` of the expected rows the mean is blended into (needs mean)
 };
 
 // which form a pass over n rows takes, and its block size
@@ -159,6 +161,8 @@ int run_blocks(gnn_mlp_group *g, const ResidentSet &rs, int64_t first, int64_t n
         hipLaunchKernelGGL(group_combine_kernel, dim3((unsigned)nb), dim3(256), 0, h0->stream, cp);
         HIP_TRY(hipGetLastError());
         slot += nb;
+        if (o.blend_y) // (distill_kernel.h; the block's expected rows, which the forward and combine launches above have read)
+            HIP_TRY(launch_blend(BlendParams{cp.mean_out, o.blend_y + (size_t)off * ldo, ldo, d_out, B, o.keep}, h0->stream));
         if (o.confusion) { // the tables the combine kernel just read, then the ensemble's labels of this block
             ConfusionParams cf{};
             for (int k = 0; k < g->K; k++) cf.label[k] = cp.label[k];
@@ -248,6 +252,28 @@ int prepare_group_point(gnn_mlp_group *g, int64_t n) {
         EvalScope scope(h, form.block, &rc);
         if (rc != GNN_OK) return rc;
     }
+    return GNN_OK;
+}
+// gnn_mlp_group_ensemble_set_range's pass over another handle's rows, the mean kept on the device and blended block by block
+int group_distill_rows(gnn_mlp_group *g, const ResidentSet &rs, int64_t first, int64_t n, float *y_rows, float keep) {
+    const gnn_mlp *h0 = g->m[0];
+    const int K = g->K, ns = n_slots_for(g, n), d_out = h0->dims[h0->L - 1];
+    const size_t head = sizeof(unsigned long long) * (size_t)(K + 1) + sizeof(double) * (size_t)K;
+    const size_t slots_b = sizeof(double) * (size_t)ns * GE_GROUP_MAX;
+    DevScratch res;
+    TRY(res.alloc(head + slots_b + sizeof(float) * (size_t)n * d_out));
+    hipStream_t st = h0->stream;
+    HIP_TRY(hipMemsetAsync(res.p, 0, head, st));
+    EvalOut o{};
+    o.hits = res.as<unsigned long long>();
+    o.sums = reinterpret_cast<double *>(o.hits + (K + 1));
+    o.slots = o.sums + K;
+    o.mean = reinterpret_cast<float *>(res.as<char>() + head + slots_b);
+    o.blend_y = y_rows; o.keep = keep;
+    const int rc = run_blocks(g, rs, first, n, o);
+    const hipError_t e = hipStreamSynchronize(st); // (also on failure: the scratch is released when this function returns)
+    if (rc != GNN_OK) return rc;
+    if (e != hipSuccess) return fail(GNN_ERR_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
     return GNN_OK;
 }
 int enqueue_group_point(gnn_mlp_group *g, int64_t n, unsigned long long *d_hits, double *d_sums, double *d_slots) {

@@ -186,6 +186,7 @@ struct gnn_mlp {
     char *arena_lo = nullptr; size_t arena_bytes = 0; // this handle's slice of the group's arena: never freed by the handle
     bool shared_dataset = false; // DX / DY / DXb are member 0's (the group's one copy)
     bool shared_stream = false;  // own_stream is the group's
+    bool dp_replica = false;     // a replica of a gnn_mlp_dp_t (dp.hip): borrowed, its resident rows are the data-parallel handle's
 
     hipError_t launch_error = hipSuccess; // first refused launch of a module / function-pointer kernel since the last check
     const int32_t *cur_idx = nullptr; // device row indices of the batch being stepped (fused path reads rows through them)
@@ -250,6 +251,10 @@ void free_group_eval(gnn_mlp_group *g);
 int enqueue_group_validation(gnn_mlp_group *g, int n, float *loss_rows, int64_t stride);
 // ... and n_rows x K such rows summed: d_out[i * K + k] = the fp64 sum of the first n entries of row (i, k)
 int enqueue_group_curve_sum(gnn_mlp_group *g, const float *rows, int n_rows, int64_t stride, int n, double *d_out);
+// gnn_mlp_group_distill_range's pass (distill.hip), synchronous: rows [first, first + n) of `rs` -- another handle's resident set --
+// through gnn_mlp_group_ensemble_range's launches, and behind every block's combine launch the mean rows blended into the
+// expected rows y_rows (row `first` of rs.Y; distill_kernel.h).  The caller has checked everything.
+int group_distill_rows(gnn_mlp_group *g, const ResidentSet &rs, int64_t first, int64_t n, float *y_rows, float keep);
 
 // ---- error convention (abi.hip) ---------------------------------------------------------------
 int fail(int code, const std::string &msg);   // records the calling thread's message, returns `code`
@@ -264,6 +269,11 @@ void unpack_params(const gnn_mlp *h, const std::vector<float> &in, double *flat)
 // the training set or the held-out set of a handle (GNN_SET_*), as the evaluation passes read them
 inline ResidentSet resident_set(const gnn_mlp *h, int set) {
     return set == GNN_SET_HELD_OUT ? h->held : ResidentSet{h->DX, h->DY, h->DXb, h->dataset_n};
+}
+// what an upload (and gnn_mlp_set_targets_range) on a member of a group is refused with
+inline const char *member_set_message(int set) {
+    return set == GNN_SET_HELD_OUT ? "a member of a group sees the group's held-out set (gnn_mlp_group_upload_held_out)"
+                                   : "a member of a group trains on the group's dataset (gnn_mlp_group_upload_dataset)";
 }
 // ... and the status for a `set` that is neither, a set never uploaded, rows outside it
 int check_set_rows(const gnn_mlp *h, int set, int64_t first, int64_t n);

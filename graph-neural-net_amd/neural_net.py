@@ -81,6 +81,19 @@ def best_point(hits, loss, rule="loss"):
     return at
 
 
+def smooth_labels(labels, d_out, eps):
+    """Label smoothing on the host: rows (1 - eps) * onehot(label) + eps / d_out, (n, d_out) fp64 -- targets for set_targets."""
+    labels = np.asarray(labels).astype(np.int64).ravel()
+    d_out, eps = int(d_out), float(eps)
+    if labels.size and (labels.min() < 0 or labels.max() >= d_out):
+        raise ValueError("labels outside [0, %d)" % d_out)
+    if not 0.0 <= eps <= 1.0:
+        raise ValueError("eps must lie in [0, 1]")
+    out = np.full((labels.size, d_out), eps / d_out, dtype=np.float64)
+    out[np.arange(labels.size), labels] += 1.0 - eps
+    return out
+
+
 class NeuralNet:
     """NeuralNet.java:7-67 -- propagate / calculateLoss / calculateWeightGradient /
     gradientStep / getInputDim / getOutputDim, batched: a 2-D array is a batch of rows."""
@@ -277,6 +290,11 @@ class NeuralNet:
             _rule(rule), hits.ctypes.data_as(C.POINTER(C.c_int64)), _dp(loss), C.byref(best), _dp(w) if weights else None))
         return hits, loss, int(best.value), (w if weights and best.value >= 0 else None)
 
+    def train_sampled(self, sampler, iterations, batch, step, momentum, noise=False):
+        """The loop NNT:82-90 on the resident rows: `iterations` times { sampler.sample(batch); gradientStep }, on the device."""
+        _capi.check(self._lib.gnn_mlp_train_sampled(self._h, sampler._h, int(iterations), int(batch), float(step),
+                                                    float(momentum), int(bool(noise))))
+
     def gradient_step_indexed(self, idx, step, momentum, noise=False):
         idx = np.ascontiguousarray(idx, dtype=np.int32).ravel()
         _capi.check(self._lib.gnn_mlp_gradient_step_indexed(
@@ -350,6 +368,42 @@ class NeuralNet:
         _capi.check(self._lib.gnn_mlp_evaluate_set_range(self._h, int(bool(held_out)), first, n, None, None, None,
                                                          lab.ctypes.data_as(C.POINTER(C.c_int32))))
         return lab
+
+    # -- targets of resident rows: csrc/distill.hip ---------------------------------------------------
+    def get_targets(self, first=0, n=None, held_out=False):
+        """The expected rows [first, first + n) the device holds, (n, d_out): the fp64 of their f32 values."""
+        first, n = self._rows(first, n, held_out)
+        out = np.empty((max(n, 0), self.layer_dims[-1]), dtype=np.float64)
+        _capi.check(self._lib.gnn_mlp_get_targets_range(self._h, int(bool(held_out)), first, n, _dp(out)))
+        return out
+
+    def set_targets(self, Y, first=0, held_out=False):
+        """Rewrites the expected rows [first, first + len(Y)) in place (label smoothing, a teacher's outputs, free values): the
+        handle then behaves bit for bit as if the set had been uploaded with them.  Inputs and look-ahead state are untouched."""
+        Y = _f64(Y, self.layer_dims[-1])
+        _capi.check(self._lib.gnn_mlp_set_targets_range(self._h, int(bool(held_out)), int(first), Y.shape[0], _dp(Y)))
+
+    def propagate_range(self, first=0, n=None, held_out=False):
+        """propagate() (NN:16) over resident rows [first, first + n), (n, d_out): the output rows of evaluate_range's pass, of
+        which labels_range is the `>=` argmax; one readback."""
+        first, n = self._rows(first, n, held_out)
+        out = np.empty((max(n, 0), self.layer_dims[-1]), dtype=np.float64)
+        _capi.check(self._lib.gnn_mlp_propagate_set_range(self._h, int(bool(held_out)), first, n, _dp(out)))
+        return out
+
+    def distill_from(self, teacher, keep=0.0, first=0, n=None):
+        """Blends a teacher's outputs on THIS net's resident input rows into its expected rows, on the device:
+        y' = keep * y + (1 - keep) * t in f32 over training rows [first, first + n).  `teacher` is a NeuralNet (t = its
+        propagate_range on these rows) or a NetGroup (t = the ensemble's mean output); only input width, output width, inner
+        activation, dtype and device must agree.  keep=1 changes nothing, keep=0 stores the teacher's rows.  Accuracy on the
+        training set means nothing afterwards (hits follow the last exact 1.0 of a row); the held-out set stays the measure."""
+        first, n = self._rows(first, n)
+        if isinstance(teacher, NetGroup):
+            _capi.check(self._lib.gnn_mlp_group_distill_range(self._h, teacher._h, first, n, float(keep)))
+        elif isinstance(teacher, NeuralNet):
+            _capi.check(self._lib.gnn_mlp_distill_range(self._h, teacher._h, first, n, float(keep)))
+        else:
+            raise TypeError("teacher: a NeuralNet or a NetGroup, got %r" % (type(teacher).__name__,))
 
     # -- which inputs the loss depends on: csrc/input_grad_kernel.h ----------------------------------
     def input_gradient(self, X, Y):
@@ -626,6 +680,11 @@ class NetGroup:
     @property
     def held_out_size(self):
         return self.members[0].held_out_size
+
+    def set_targets(self, Y, first=0, held_out=False):
+        """NeuralNet.set_targets on the group's ONE copy of the rows (members[k].get_targets reads it)."""
+        Y = _f64(Y, self.layer_dims[-1])
+        _capi.check(self._lib.gnn_mlp_group_set_targets_range(self._h, int(bool(held_out)), int(first), Y.shape[0], _dp(Y)))
 
     def train_sampled_held_out(self, samplers, iterations, batches, steps, momenta, every, held_rows=None, rule="loss", weights=True):
         """train_sampled with one sampler and one batch size per member (a scalar `batches`: one size for all), the held-out

@@ -491,6 +491,45 @@ int gnn_mlp_group_train_sampled_held_out(gnn_mlp_group_t *g, gnn_sampler_t *cons
                                          int64_t *ensemble_hits /* [P] or null */,
                                          int32_t *best_point /* [K] */, double *best_weights /* [K][num_params] or null */);
 
+/* ---- targets of resident rows ---------------------------------------------------------------------
+ * The expected rows of a resident set (gnn_data_set) read back, rewritten in place, and written ON THE DEVICE from a teacher's
+ * outputs -- the classic use of an ensemble: train one small net on the ensemble's outputs (csrc/distill.hip,
+ * csrc/distill_kernel.h).  Nothing here reallocates a set, touches an input row or changes the look-ahead state: what a handle
+ * prepares ahead reads input rows only.  With these calls unused every result is bit for bit what it was. */
+/* Y[i * d_out + c] = the fp64 of the f32 expected value the device holds for row first + i.  Works on borrowed handles (a
+ * member of a group reads the group's one copy).  A `set` that is neither value, rows outside the set -> GNN_ERR_BAD_ARG; the
+ * named set never uploaded -> GNN_ERR_STATE. */
+int gnn_mlp_get_targets_range(gnn_mlp_t *h, int set, int64_t first, int64_t n, double *Y /* [n][d_out] */);
+/* Rewrites the expected rows [first, first + n) of the named set, converted to f32 exactly as gnn_mlp_upload_dataset converts
+ * its Y; every other row, the padding and the inputs stay as they are; no allocation.  Ordered behind everything in flight on
+ * the handle's stream; a deferred host-batch update is applied first.  Afterwards the handle behaves bit for bit like one whose
+ * set was uploaded with those targets in the first place -- also with a gnn_mlp_hint_next_range pending.  Refusals as above;
+ * on a member of a group -> GNN_ERR_STATE (the group call writes the one copy). */
+int gnn_mlp_set_targets_range(gnn_mlp_t *h, int set, int64_t first, int64_t n, const double *Y);
+int gnn_mlp_group_set_targets_range(gnn_mlp_group_t *g, int set, int64_t first, int64_t n, const double *Y);
+/* NN:16 propagate() over rows [first, first + n) of the named set, any n: the output rows of the evaluation pass -- the blocks
+ * and launches of gnn_mlp_evaluate_set_range, whose labels are the `>=` argmax (MT:166-168) of these rows, bit for bit --
+ * collected on the device and read back once (fp64 of the f32 outputs).  Writes no weight, momentum, step count or look-ahead
+ * state.  Works on borrowed handles. */
+int gnn_mlp_propagate_set_range(gnn_mlp_t *h, int set, int64_t first, int64_t n, double *out /* [n][d_out] */);
+/* Distillation on the device.  For every row r in [first, first + n) of the STUDENT's training set and every class c:
+ *   y'[r][c] = keep_f * y[r][c] + (1.f - keep_f) * t[r][c]      in f32, keep_f = (float)keep, no fused multiply-add,
+ * t = the teacher's output on the student's resident input row r: for a net what gnn_mlp_propagate_set_range returns on those
+ * rows, for a group the mean output as gnn_mlp_group_ensemble_range forms it (f32, member order, one division by (float)K;
+ * groups off the grouped evaluation plan run member after member into the same blend).  The teacher runs its usual evaluation
+ * pass with the student's rows as its data set, and one more launch per block of rows blends into the student's expected rows.
+ * keep == 1 leaves every bit unchanged, keep == 0 makes the rows bit for bit the f32 teacher output; padding stays zero.
+ * Synchronous: the student's stream is synchronised before the teacher's stream writes, the teacher's before the call returns.
+ * The teacher's weights, momentum, step count and look-ahead state are untouched (its deferred host-batch update is applied
+ * first); teacher == student is allowed.  Hidden layers, depth and output kind may differ.  Refused before any work: a null
+ * handle, keep outside [0, 1] or NaN, rows outside the set, teacher and student differing in dims[0], dims[L-1], inner
+ * activation, dtype or device (the message names which) -> GNN_ERR_BAD_ARG; no training set on the student, a student that is
+ * a member of a group or a replica of a gnn_mlp_dp_t -> GNN_ERR_STATE.
+ * Hit counts on a set whose targets are no longer one-hot follow the expected-class rule (the last exact 1.0, else class 0):
+ * accuracy on the training set means nothing after this call; the held-out set is untouched and stays the measure. */
+int gnn_mlp_distill_range(gnn_mlp_t *student, gnn_mlp_t *teacher, int64_t first, int64_t n, double keep);
+int gnn_mlp_group_distill_range(gnn_mlp_t *student, gnn_mlp_group_t *teachers, int64_t first, int64_t n, double keep);
+
 /* ---- shape specialisation ---------------------------------------------------------------------
  * The per-row-block kernel of the fused small-net path is a template over the net's shape; with
  * compile-time layer sizes it is ~1.5x faster than with sizes read from kernel arguments.
