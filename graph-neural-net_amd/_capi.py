@@ -121,6 +121,10 @@ SYMBOLS = [
     ("gnn_mlp_propagate_set_range", C.c_int, [_H, C.c_int, C.c_int64, C.c_int64, _dp]),
     ("gnn_mlp_distill_range", C.c_int, [_H, _H, C.c_int64, C.c_int64, C.c_double]),
     ("gnn_mlp_group_distill_range", C.c_int, [_H, _H, C.c_int64, C.c_int64, C.c_double]),
+    ("gnn_mlp_fgsm_set_range", C.c_int, [_H, C.c_int, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double, _dp]),
+    ("gnn_mlp_evaluate_fgsm_set_range", C.c_int, [_H, C.c_int, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double,
+                                                  C.POINTER(C.c_int64), _dp]),
+    ("gnn_mlp_train_sampled_fgsm", C.c_int, [_H, _H, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double]),
     ("gnn_mlp_forget_lookahead", C.c_int, [_H]),
     ("gnn_mlp_advance_time", C.c_int, [_H, C.c_int]),
     ("gnn_mlp_recover_stream", C.c_int, [_H]),

@@ -485,6 +485,11 @@ struct EvalScope { // for blocks above max_batch: the evaluation workspace's buf
 };
 void free_eval_workspace(gnn_mlp *h);
 void free_input_grad(gnn_mlp *h); // (input_grad.hip; destroy_handle calls it)
+// input_grad.hip: behind a do_gradient on (a0, B), the launch over delta_1 . W_0^T -- the block's input gradient into h->gx
+// (the caller has made it), or with `fgsm` the rows a0 perturbed along its sign into fgsm->out (input_grad_kernel.h: fgsm_kernel;
+// out == a0 is allowed)
+struct FgsmStep { float eps, lo, hi; float *out; };
+void enqueue_input_grad(gnn_mlp *h, const float *a0, int B, const FgsmStep *fgsm = nullptr);
 void rccl_detach_handle(gnn_mlp *h); // (dp.hip; gnn_mlp_destroy calls it)
 bool can_defer_update(const gnn_mlp *h);
 int step_on_host_batch_deferred(gnn_mlp *h, int B, double step, double momentum); // act[0] / ybuf hold the staged batch
@@ -523,10 +528,16 @@ struct SampledEach {
     virtual void step_sizes(const int *rows, const int *next_rows) { (void)rows; (void)next_rows; }
     virtual ~SampledEach() {}
 };
+// What steps an iteration INSTEAD of step_on_device_indices (a lone handle's call; adversarial.hip: the batch is perturbed first):
+// nothing is announced to the look-ahead state then, the draws, chunks and uploads are the loop's own.
+struct SampledStep {
+    virtual int step(const int32_t *d_idx, int B) = 0;
+    virtual ~SampledStep() {}
+};
 // The loop itself, for n samplers (a lone handle: &s, 1, &batch, each null).  batches[m]: sampler m's nominal batch size (all
 // equal unless each->sized()); every ring has the slot stride of the largest (index_ring.h)
 int train_sampled_run(gnn_mlp *h, gnn_sampler_t *const *samplers, int n, int iterations, const int *batches, double step,
-                      double momentum, int noise, SampledObserver *obs, SampledEach *each);
+                      double momentum, int noise, SampledObserver *obs, SampledEach *each, SampledStep *stepper = nullptr);
 // the held-out curve (sampler.hip; keep_best_kernel.h): a handle's snapshot buffer and history for `points` points, the launch for
 // K nets of one shape, the arguments both entry points refuse
 int ensure_keep_best(gnn_mlp *h, int points);

@@ -24,23 +24,6 @@ int ensure_gx(gnn_mlp *h) {
     return GNN_OK;
 }
 
-// gx = (delta_1 . W_0^T) * f'(a0) of the block do_gradient has just run on
-void enqueue_input_grad(gnn_mlp *h, const float *a0, int B) {
-    const bool bf = h->dtype == GNN_DTYPE_BF16;
-    InputGradParams p{};
-    p.D = bf ? static_cast<const void *>(h->deltab[1]) : static_cast<const void *>(h->delta[1]);
-    p.W = bf ? static_cast<const void *>(h->Wb + h->w_off[0]) : static_cast<const void *>(h->W + h->w_off[0]);
-    p.A0 = a0; p.lda = h->ld[0];
-    p.GX = h->gx; p.ldg = h->ld[0];
-    p.M = h->ld[0]; p.m_true = h->dims[0];
-    p.K = h->ld[1];
-    p.rows = B;
-    p.act = h->inner_act;
-    const dim3 grid((unsigned)((h->ld[0] / 16 + IG_WAVES - 1) / IG_WAVES), (unsigned)(pad_up(B) / 16));
-    if (bf) hipLaunchKernelGGL(input_grad_kernel<true>, grid, dim3(IG_WAVES * 64), 0, h->stream, p);
-    else hipLaunchKernelGGL(input_grad_kernel<false>, grid, dim3(IG_WAVES * 64), 0, h->stream, p);
-}
-
 // sal[c][i] += |gx[b][i]| over the block's rows of class c, class_rows[c] += their number (either may be null, not both)
 void enqueue_saliency(const gnn_mlp *h, hipStream_t stream, const float *gx, const float *y, int B, double *sal,
                       unsigned long long *class_rows) {
@@ -75,6 +58,29 @@ void widen(const float *src, double *dst, size_t n) {
 
 namespace gnn {
 namespace host {
+// gx = (delta_1 . W_0^T) * f'(a0) of the block do_gradient has just run on -- or, `fgsm`, the rows perturbed along the sign of
+// that gradient into fgsm->out (fgsm_kernel; gx is then neither needed nor written)
+void enqueue_input_grad(gnn_mlp *h, const float *a0, int B, const FgsmStep *fgsm) {
+    const bool bf = h->dtype == GNN_DTYPE_BF16;
+    InputGradParams p{};
+    p.D = bf ? static_cast<const void *>(h->deltab[1]) : static_cast<const void *>(h->delta[1]);
+    p.W = bf ? static_cast<const void *>(h->Wb + h->w_off[0]) : static_cast<const void *>(h->W + h->w_off[0]);
+    p.A0 = a0; p.lda = h->ld[0];
+    p.GX = fgsm ? fgsm->out : h->gx; p.ldg = h->ld[0];
+    p.M = h->ld[0]; p.m_true = h->dims[0];
+    p.K = h->ld[1];
+    p.rows = B;
+    p.act = h->inner_act;
+    const dim3 grid((unsigned)((h->ld[0] / 16 + IG_WAVES - 1) / IG_WAVES), (unsigned)(pad_up(B) / 16));
+    if (fgsm) {
+        const FgsmParams q{p, fgsm->eps, fgsm->lo, fgsm->hi};
+        if (bf) hipLaunchKernelGGL(fgsm_kernel<true>, grid, dim3(IG_WAVES * 64), 0, h->stream, q);
+        else hipLaunchKernelGGL(fgsm_kernel<false>, grid, dim3(IG_WAVES * 64), 0, h->stream, q);
+        return;
+    }
+    if (bf) hipLaunchKernelGGL(input_grad_kernel<true>, grid, dim3(IG_WAVES * 64), 0, h->stream, p);
+    else hipLaunchKernelGGL(input_grad_kernel<false>, grid, dim3(IG_WAVES * 64), 0, h->stream, p);
+}
 void free_input_grad(gnn_mlp *h) {
     if (h->gx) (void)hipFree(h->gx);
     h->gx = nullptr;

@@ -1,6 +1,6 @@
 // input_grad_kernel.h -- which inputs the loss depends on: g = d calculateLoss(x, y) / d x (NN:27, SCE:207-220, GNN:230-242),
 // the l = 0 continuation of the backward loop the reference stops at delta_1 (SCE:272-278), and what consumes it on the device
-// (input_grad.hip: gnn_mlp_input_gradient*, gnn_mlp_group_input_gradient_range).
+// (input_grad.hip: gnn_mlp_input_gradient*, gnn_mlp_group_input_gradient_range; adversarial.hip: gnn_mlp_fgsm_set_range ...).
 //   input_grad_kernel<BF>      gx[b][i] = f'(a0[b][i]) * sum_j delta_1[b][j] * W_0[i][j]: pad(B) rows, ld[0] columns, contraction
 //                              over ld[1].  f' from a0 = f(x) (the reference applies f to the raw input too, SCE:183-186): for the
 //                              leaky pair `a <= 0 ? 0.01 : 1` (MT:235), so an exact-zero pixel gets 0.01.  Both operands are
@@ -14,6 +14,7 @@
 //                              to f32 on the way into v_mfma_f32_16x16x4_f32 -- a product of two bf16 values is exact in f32, the
 //                              accumulation is f32 either way, and one kernel body serves both; f' from the unrounded a0.
 //                              Rows >= `rows` and columns >= m_true are written as exact zeros (W_0's pad rows are 0).
+//   fgsm_kernel<BF>            the same product (ig_tile_product) with the perturbation a0 + eps * sign(g), clipped, as its epilogue
 //   saliency_kernel            thread (column i, class c) walks the block's rows in row order and adds (double)|gx[b][i]| of the
 //                              rows whose expected class (confusion_kernel.h: expected_class, MT:186-188) is c into sal[c][i];
 //                              the running sum starts from the value the previous block left, so over a range it is ONE sum in row
@@ -52,13 +53,9 @@ template <bool BF> __device__ __forceinline__ f32x4 ig_load4(const void *base, s
     }
 }
 
-// grid: (ceil(M / 16 / IG_WAVES), pad(rows) / 16)
-template <bool BF>
-static __global__ __launch_bounds__(IG_WAVES * 64) void input_grad_kernel(InputGradParams p) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int fr = lane & 15, fq = lane >> 4;
-    const int i0 = (blockIdx.x * IG_WAVES + wave) * 16, b0 = blockIdx.y * 16;
-    if (i0 >= p.M) return; // (no barrier below)
+// One wave's 16 x 16 tile of delta_1 . W_0^T at (input columns i0.., batch rows b0..): the loads and the accumulation order every
+// kernel over this product shares (input_grad_kernel, fgsm_kernel), so that their g agree bit for bit
+template <bool BF> __device__ __forceinline__ f32x4 ig_tile_product(const InputGradParams &p, int i0, int b0, int fr, int fq) {
     const size_t w_at = (size_t)(i0 + fr) * p.K + 4 * fq, d_at = (size_t)(b0 + fr) * p.K + 4 * fq;
     const int nc = p.K / 16;
     f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
@@ -83,7 +80,17 @@ static __global__ __launch_bounds__(IG_WAVES * 64) void input_grad_kernel(InputG
             }
         }
     }
-    const f32x4 acc = acc0 + acc1;
+    return acc0 + acc1;
+}
+
+// grid: (ceil(M / 16 / IG_WAVES), pad(rows) / 16)
+template <bool BF>
+static __global__ __launch_bounds__(IG_WAVES * 64) void input_grad_kernel(InputGradParams p) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int fr = lane & 15, fq = lane >> 4;
+    const int i0 = (blockIdx.x * IG_WAVES + wave) * 16, b0 = blockIdx.y * 16;
+    if (i0 >= p.M) return; // (no barrier below)
+    const f32x4 acc = ig_tile_product<BF>(p, i0, b0, fr, fq);
     // C / D layout: column (here: batch row) = lane & 15, rows (here: input columns) = 4 * (lane >> 4) + r
     const int b = b0 + fr, col = i0 + 4 * fq;
     f32x4 o = {0.f, 0.f, 0.f, 0.f};
@@ -91,6 +98,42 @@ static __global__ __launch_bounds__(IG_WAVES * 64) void input_grad_kernel(InputG
         const f32x4 a = *reinterpret_cast<const f32x4 *>(p.A0 + (size_t)b * p.lda + col);
 #pragma unroll
         for (int r = 0; r < 4; r++) o[r] = col + r < p.m_true ? acc[r] * act_prime_from_a(p.act, a[r]) : 0.f;
+    }
+    *reinterpret_cast<f32x4 *>(p.GX + (size_t)b * p.ldg + col) = o;
+}
+
+// The fast-gradient-sign perturbation (adversarial.hip) as the epilogue of the same product: g is formed exactly as above and
+// never stored; what is stored, into a ROWS buffer (g.GX, leading dimension g.ldg -- the handle's act[0]), is
+//   a' = min(max(a0 + eps * s(g), lo), hi),   s(g) = (g > 0) - (g < 0)
+// in f32, every operation rounded on its own.  s(0) = 0 and a NaN g leave the element unperturbed (clipped only).
+struct FgsmParams {
+    InputGradParams g; // GX / ldg: the perturbed rows
+    float eps, lo, hi;
+};
+__device__ inline float fgsm_value(float a, float g, float eps, float lo, float hi) {
+#pragma clang fp contract(off) // (a + eps * s must not become an fma: the formula rounds the product)
+    const float s = g > 0.f ? 1.f : g < 0.f ? -1.f : 0.f;
+    const float t = eps * s;
+    const float v = a + t;
+    return fminf(fmaxf(v, lo), hi);
+}
+// grid as input_grad_kernel's.  In place (g.GX == g.A0, the host-batch case) is safe: a lane reads its own four a0 values, and
+// nothing else of A0, before it stores the same four cells; rows >= `rows` and columns >= m_true become exact zeros.
+template <bool BF>
+static __global__ __launch_bounds__(IG_WAVES * 64) void fgsm_kernel(FgsmParams q) {
+    const InputGradParams &p = q.g;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int fr = lane & 15, fq = lane >> 4;
+    const int i0 = (blockIdx.x * IG_WAVES + wave) * 16, b0 = blockIdx.y * 16;
+    if (i0 >= p.M) return; // (no barrier below)
+    const f32x4 acc = ig_tile_product<BF>(p, i0, b0, fr, fq);
+    const int b = b0 + fr, col = i0 + 4 * fq;
+    f32x4 o = {0.f, 0.f, 0.f, 0.f};
+    if (b < p.rows) {
+        const f32x4 a = *reinterpret_cast<const f32x4 *>(p.A0 + (size_t)b * p.lda + col);
+#pragma unroll
+        for (int r = 0; r < 4; r++)
+            o[r] = col + r < p.m_true ? fgsm_value(a[r], acc[r] * act_prime_from_a(p.act, a[r]), q.eps, q.lo, q.hi) : 0.f;
     }
     *reinterpret_cast<f32x4 *>(p.GX + (size_t)b * p.ldg + col) = o;
 }

@@ -240,11 +240,11 @@ struct DeviceIndexRing {
 // n > 1: `each`, a group call with one sampler per member on member 0's handle.  Sampler m draws batches of batches[m] into
 // ring m, and an iteration whose n batch sizes differ is handed to each->mixed_step instead of being stepped here -- unless
 // each->sized(): the grouped launches then take every member's own size (each->step_sizes) and every iteration is stepped here.
-// Unless sized, the n nominal sizes are equal.
+// Unless sized, the n nominal sizes are equal.  `stepper` (lone handles): it steps every iteration in place of step_on_device_indices.
 int gnn::host::train_sampled_run(gnn_mlp *h, gnn_sampler_t *const *samplers, int n, int iterations, const int *batches, double step,
-                                 double momentum, int noise, SampledObserver *obs, SampledEach *each) {
+                                 double momentum, int noise, SampledObserver *obs, SampledEach *each, SampledStep *stepper) {
     TRY(check_handle(h));
-    if (n < 1 || n > GROUP_MAX || (n > 1 && !each)) return fail(GNN_ERR_BAD_ARG, "bad sampler count");
+    if (n < 1 || n > GROUP_MAX || (n > 1 && !each) || (stepper && each)) return fail(GNN_ERR_BAD_ARG, "bad sampler count");
     const bool sized = each && each->sized();
     int batch = batches[0]; // the largest nominal size: the slot stride of every ring, so that member k's index pointer stays member 0's + k * idx_S
     for (int m = 0; m < n; m++) {
@@ -283,9 +283,11 @@ int gnn::host::train_sampled_run(gnn_mlp *h, gnn_sampler_t *const *samplers, int
         const int i0 = sched.begin(c), len = sched.length(c);
         for (int at = 0; at < len && rc == GNN_OK; at++) {
             const DeviceIndexRing::Iteration it = ring.iteration(RingPos{c, at});
-            const RingPos next = h->chain ? ring.win.successor(c, at) : RingPos{};
+            const RingPos next = h->chain && !stepper ? ring.win.successor(c, at) : RingPos{};
             const DeviceIndexRing::Iteration nx = next ? ring.iteration(next) : DeviceIndexRing::Iteration{}; // the one to announce, if it is on the device already
-            if (!sized && !it.same) { // the members' batches differ in size (a refill shortened some): member after member, nothing announced
+            if (stepper) { // (handle.h: SampledStep)
+                rc = stepper->step(it.idx0, it.counts[0]);
+            } else if (!sized && !it.same) { // the members' batches differ in size (a refill shortened some): member after member, nothing announced
                 const int32_t *idx[GROUP_MAX];
                 for (int m = 0; m < n; m++) idx[m] = ring.indices(m, c, at);
                 rc = each->mixed_step(idx, it.counts);

@@ -436,6 +436,33 @@ class NeuralNet:
             return g
         return (g, sal, rows) if grad else (sal, rows)
 
+    # -- adversarial rows on the device: csrc/adversarial.hip -----------------------------------------
+    # x' = clip(x + eps * sign(input gradient), lo, hi) in f32 on the rows the device holds.  Needs an inner activation that is the
+    # identity on non-negative values (leaky ReLU, ReLU, identity), 0 <= lo <= hi, and -- unchecked -- non-negative rows.
+    def fgsm_range(self, eps, first=0, n=None, clip=(0.0, 1.0), held_out=False):
+        """The perturbed rows [first, first + n), (n, d_0): element for element clip(float32(x) + float32(eps) * sign(g)) with g
+        the value input_gradient_range returns; one readback."""
+        first, n = self._rows(first, n, held_out)
+        out = np.empty((max(n, 0), self.layer_dims[0]), dtype=np.float64)
+        _capi.check(self._lib.gnn_mlp_fgsm_set_range(self._h, int(bool(held_out)), first, n, float(eps), float(clip[0]),
+                                                     float(clip[1]), _dp(out)))
+        return out
+
+    def evaluate_fgsm_range(self, eps, first=0, n=None, clip=(0.0, 1.0), held_out=False):
+        """Robust (hits, loss_sum): evaluate_range's counts on the perturbed rows, each block perturbed against the current
+        weights and never leaving the device."""
+        first, n = self._rows(first, n, held_out)
+        hits, loss = C.c_int64(), C.c_double()
+        _capi.check(self._lib.gnn_mlp_evaluate_fgsm_set_range(self._h, int(bool(held_out)), first, n, float(eps), float(clip[0]),
+                                                              float(clip[1]), C.byref(hits), C.byref(loss)))
+        return hits.value, loss.value
+
+    def train_sampled_fgsm(self, sampler, iterations, batch, step, momentum, eps, clip=(0.0, 1.0)):
+        """Adversarial training: train_sampled's loop, every iteration stepping on the perturbation of its own batch against the
+        weights of that moment."""
+        _capi.check(self._lib.gnn_mlp_train_sampled_fgsm(self._h, sampler._h, int(iterations), int(batch), float(step),
+                                                         float(momentum), float(eps), float(clip[0]), float(clip[1])))
+
     # -- data-parallel hooks ------------------------------------------------------------------
     @property
     def grad_elems(self):

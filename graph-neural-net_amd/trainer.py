@@ -245,7 +245,9 @@ def per_class(conf):
 
 def fgsm(net, X, Y, eps, clip=(0.0, 1.0)):
     """The fast-gradient-sign perturbation of the rows: clip(X + eps * sign(g)), g = net.input_gradient(X, Y).  Computed on the
-    host: the device holds f(x), not x.  clip=None leaves the rows unclipped."""
+    host, in fp64, for any inner activation (the device holds f(x), not x); clip=None leaves the rows unclipped.  For rows that
+    are RESIDENT, non-negative and behind an inner activation that is the identity there (leaky ReLU, ReLU, identity) the device
+    forms the same perturbation in f32 without a round trip: NeuralNet.fgsm_range, evaluate_fgsm_range, train_sampled_fgsm."""
     X = np.asarray(X, dtype=np.float64)
     out = X + float(eps) * np.sign(net.input_gradient(X, Y))
     return out if clip is None else np.clip(out, clip[0], clip[1])

@@ -530,6 +530,38 @@ int gnn_mlp_propagate_set_range(gnn_mlp_t *h, int set, int64_t first, int64_t n,
 int gnn_mlp_distill_range(gnn_mlp_t *student, gnn_mlp_t *teacher, int64_t first, int64_t n, double keep);
 int gnn_mlp_group_distill_range(gnn_mlp_t *student, gnn_mlp_group_t *teachers, int64_t first, int64_t n, double keep);
 
+/* ---- adversarial rows (fast gradient sign) --------------------------------------------------------
+ * The perturbation x' = clip(x + eps * sign(g), lo, hi), g = d calculateLoss(x, y) / d x (NN:27, SCE:207-220, GNN:230-242; the
+ * gradient gnn_mlp_input_gradient_range returns), formed ON THE DEVICE from the rows it holds (csrc/adversarial.hip; the kernel:
+ * csrc/input_grad_kernel.h, fgsm_kernel).  Per element, in f32 with every operation rounded on its own (no fused multiply-add):
+ *   a' = min(max(a + eps_f * s, lo_f), hi_f),   s = (g > 0) - (g < 0)
+ * with g bit for bit the value gnn_mlp_input_gradient_range returns for the element: s(0) = 0, a NaN g leaves the element
+ * unperturbed; eps == 0 returns rows inside [lo, hi] bit for bit.  The device holds a = f(x), not x (the reference applies f to
+ * the raw input too, SCE:183-186), so the calls serve the inner activations that are the identity on non-negative values --
+ * leaky ReLU (MT:235), ReLU, identity -- with 0 <= lo <= hi, and it is the caller's PRECONDITION, not checked, that the rows are
+ * non-negative (rows uploaded with gnn_mlp_upload_dataset_u8 always are).  Lone nets of either dtype on every plan; a member of a
+ * group or a replica of a gnn_mlp_dp_t -> GNN_ERR_STATE.  A sigmoid or tanh inner activation -> GNN_ERR_UNSUPPORTED; eps
+ * negative or not finite, lo < 0, hi < lo, a NaN bound -> GNN_ERR_BAD_ARG.  A deferred host-batch update is applied first.
+ * The two range calls work in blocks of at most max_batch rows, each the handle's gradient computation without an update plus
+ * one launch, with no host work between blocks and one readback; they change no weight, momentum, step count or sampler,
+ * overwrite the host-batch staging rows, leave the gradient buffer with the last block's weight gradient like
+ * gnn_mlp_compute_gradient*, and (training set) leave the look-ahead state as gnn_mlp_compute_gradient_range on the last block
+ * leaves it.  The named set never uploaded -> GNN_ERR_STATE; rows outside it, a `set` that is neither value -> GNN_ERR_BAD_ARG. */
+/* the perturbed rows themselves (fp64 of the f32 values) */
+int gnn_mlp_fgsm_set_range(gnn_mlp_t *h, int set, int64_t first, int64_t n, double eps, double lo, double hi,
+                           double *X_adv /* [n][d_0] */);
+/* Robust accuracy and loss (testOnTestData / testOnTrainingData, MT:159-197, and validate(), NNT:102-113, on the perturbed
+ * rows): per block the perturbation, then the forward pass and the reductions of gnn_mlp_evaluate_set_range -- the `>=` argmax
+ * (MT:166-168) against the expected class, the loss summed block after block into one slot.  Either output may be null, not both. */
+int gnn_mlp_evaluate_fgsm_set_range(gnn_mlp_t *h, int set, int64_t first, int64_t n, double eps, double lo, double hi,
+                                    int64_t *hits, double *loss_sum);
+/* Adversarial training: the loop of gnn_mlp_train_sampled (NNT:60-92; the same draws, chunks and refusals, the sampler left where
+ * that call leaves it) in which every iteration trains on the perturbation of its own batch against the weights of that moment:
+ * the drawn rows gathered into the staging rows, the gradient computation without an update, the perturbation in place, then the
+ * step (SCE:299-345) on the perturbed rows with the rows' own targets.  The step count advances once per iteration. */
+int gnn_mlp_train_sampled_fgsm(gnn_mlp_t *h, gnn_sampler_t *s, int iterations, int batch, double step, double momentum, double eps,
+                               double lo, double hi);
+
 /* ---- shape specialisation ---------------------------------------------------------------------
  * The per-row-block kernel of the fused small-net path is a template over the net's shape; with
  * compile-time layer sizes it is ~1.5x faster than with sizes read from kernel arguments.
