@@ -11,11 +11,18 @@ can tell a bookkeeping mistake from rounding -- conditions on the draw, no measu
    it shows (F8: at the first propagate behind the replacement);
 4. the f32 summation-order bound that grouped validation curves are held to against the lone nets tells a validation pass on weights
    one step old.
-The group sequences: every planted pair, every call form, and members 0, a middle one and the last stepped alone."""
+The group sequences: every planted pair, every call form, and members 0, a middle one and the last stepped alone.
+
+The second draw (tests/sequence_cases2.py: the calls merged since the first) leaves the first as it was -- a digest of every old op
+list, computed on the commit before the second draw existed, is pinned here -- and meets the same conditions for its own hazards
+H11 .. H19, its faults F9 .. F17 and its group pairs; signed perturbations leave at most adversarial_cases.UNDECIDED_CAP of the
+elements undecided at every op that is compared on the decided ones."""
 import numpy as np
 import pytest
 
+from tests import adversarial_cases as ac
 from tests import sequence_cases as sq
+from tests import sequence_cases2 as s2
 
 VOCABULARY = {"step_host", "step_range", "step_indexed", "train_range", "train_sampled", "train_observed", "compute_gradient_range",
               "apply_update", "hint", "propagate", "loss", "argmax", "loss_range", "argmax_range", "count_hits", "evaluate", "confusion",
@@ -134,3 +141,132 @@ def test_the_order_bound_tells_a_stale_validation(oracle_mod, i):
                     least = min(least, abs(a - b) / (sq.order_bound(b * V, V) / V))
     assert least >= 2.0, (case["id"], least)
     print("group sequence %s: a validation one step stale lies at least %.3g order bounds off" % (case["id"], least))
+
+
+# ---- the second draw --------------------------------------------------------------------------------------------------------------
+LONE_DIGESTS = ["75c25ffe76fc97f7", "1b74b24719e56a4b", "7ee6a3d6e54af42c", "71def35c08832125", "23fce53c224e0013", "e448bd9756f0ae0f",
+                "98356e2da66b174f", "d516100048e5815a", "df365d0aac5d890b", "90ebba3b37e61bf6", "985acede3aa467d9", "29a77b8e10a2d071",
+                "cfd3840f50e76156", "e1acc72e5d333c42", "8ae559c11c47c48a", "36265f7dff6701e4", "efbb4b42b58b9fde", "0fbba0c5e0ed61cc",
+                "f5d65805a9dd688e", "3152e1949265befe", "f1a2c6dc035e5794", "f044fb46072ae170", "675cf809943ee2cb", "a3f9028a63b2b1ef"]
+GROUP_DIGESTS = ["f5112c4edf315ca4", "c1a45f3b0fd4d66b", "01decdd94c74a2d4", "feed75540b9644f7", "f4a70e6d821fe214", "ddffffbb33682803",
+                 "5d77387f9962d512", "f773cbd97dd03975", "feeeb08080439338", "dfe8e482e9d40503", "37611419cac34cd9", "aad6526d9c6defac"]
+
+
+def test_the_first_draw_is_what_it_was():
+    """DATA_SEEDS and FAULT_FACTORS_FOUND were found on these op lists: sha256 of repr(ops), first 16 hex digits"""
+    assert [s2.digest(sq.lone_case(i)["ops"]) for i in range(sq.N_LONE)] == LONE_DIGESTS
+    assert [s2.digest(sq.group_case(i)["ops"]) for i in range(sq.N_GROUP)] == GROUP_DIGESTS
+    assert [sq.lone_case(i)["seed"] for i in range(sq.N_LONE)] == [sq.DATA_SEEDS.get(i, 9100 + i) for i in range(sq.N_LONE)]
+
+
+@pytest.fixture(scope="module")
+def modelled2(oracle_mod):
+    """the correct Model2's run of every sequence of the second draw, made once"""
+    out = {}
+    for i in range(s2.N_LONE):
+        case = s2.lone_case(i)
+        out[i] = (case,) + s2.run_model(oracle_mod, case)
+    return out
+
+
+@pytest.mark.parametrize("i", range(s2.N_LONE))
+def test_every_sequence_of_the_second_draw_contains_every_hazard(i):
+    case = s2.lone_case(i)
+    ops, fgsm = case["ops"], s2.fgsm_ok(case["inner"])
+    assert ops == s2.lone_case(i)["ops"], "the draw is not a function of its seed"
+    found = s2.hazards2(ops)
+    wanted = s2.HAZARDS_ALL + (s2.HAZARDS_FGSM if fgsm else [])
+    missing = [h for h in wanted if h not in found]
+    assert not missing, (case["id"], missing)
+    names = {name for name, _ in ops}
+    perturbing = {"fgsm_range", "evaluate_fgsm", "train_fgsm"}
+    assert names >= set(s2.NEW_OPS) - (set() if fgsm else perturbing), (case["id"], set(s2.NEW_OPS) - names)
+    assert fgsm or not names & perturbing
+    refused = {kw["kind"] for name, kw in ops if name == "refused2"}
+    assert refused == set(s2.REFUSALS) - ({"fgsm"} if fgsm else set())
+    if not fgsm:                                                # the three perturbing calls are each refused
+        assert {kw["call"] for name, kw in ops if name == "refused2" and kw["kind"] == "fgsm"} == perturbing
+    else:
+        assert {kw["signed"] for name, kw in ops if name == "fgsm_range"} == {False, True}
+        assert {kw["held"] for name, kw in ops if name in ("fgsm_range", "evaluate_fgsm")} == {False, True}
+        iters = [kw["iters"] for name, kw in ops if name == "train_fgsm"]
+        assert min(iters) <= 5 and max(iters) >= 17 and all(kw["B"] in (15, 17) for name, kw in ops if name == "train_fgsm")
+    assert {kw["size"] for name, kw in ops if name == "upload_held_out"} >= {57, 101}
+    assert {kw["teacher"] for name, kw in ops if name == "distill"} == {"self", "other", "group"}
+    assert {kw["keep"] for name, kw in ops if name == "distill"} <= set(s2.KEEPS)
+    ev = [kw for name, kw in ops if name == "evaluate_set"]
+    assert {kw["held"] for kw in ev} == {False, True} and {kw["kind"] for kw in ev} == {"evaluate", "confusion", "labels"}
+    assert any(kw["n"] > sq.MAX_BATCH for kw in ev) and any(kw["n"] <= sq.MAX_BATCH for kw in ev)
+    loops = [kw for name, kw in ops if name == "train_held_out"]
+    assert {kw["rule"] for kw in loops} == {"loss", "hits"} and any(17 <= kw["iters"] <= 20 for kw in loops)
+    assert min(kw["held_rows"] for kw in loops) < sq.MAX_BATCH < max(kw["held_rows"] for kw in loops)
+    assert {kw["every"] for kw in loops} & {3, 7} and 1 in {kw["every"] for kw in loops}
+    teacher = [kw["op"][0] for name, kw in ops if name == "teacher"]
+    assert {"hint", "step_range", "step_host", "loss_range", "get_weights"} <= set(teacher)
+    print("sequence %s: %d ops, hazards at %s" % (case["id"], len(ops), " ".join("%s@%d" % (h, found[h][0]) for h in wanted)))
+
+
+def test_the_second_draw_covers_every_choice():
+    """what one sequence need not hold, the eighteen together do"""
+    ops = [op for i in range(s2.N_LONE) for op in s2.lone_case(i)["ops"]]
+    assert {kw["every"] for name, kw in ops if name == "train_held_out"} == {1, 3, 7}
+    assert {kw["size"] for name, kw in ops if name == "upload_held_out"} == set(s2.HELD_SIZES)
+    assert {kw["keep"] for name, kw in ops if name == "distill"} == set(s2.KEEPS)
+    assert {(kw["teacher"], kw["keep"]) for name, kw in ops if name == "distill"} >= {(t, 0.0) for t in ("self", "other", "group")}
+    assert len({s2.lone_case(i)["net"] for i in range(s2.N_LONE)}) == 9 and s2.N_LONE == 18
+
+
+@pytest.mark.parametrize("i", range(s2.N_LONE))
+def test_safe_rows_and_undecided_shares_of_the_second_draw(modelled2, i):
+    case, results, _ = modelled2[i]
+    steps = [r["steps"] for r in results]
+    assert 3 in steps and 5 in steps, "no op boundary at 3 and 5 steps"
+    assert all(np.isfinite(r[k]).all() for r in results for k in ("W", "V") if k in r), "the oracle has no finite answer"
+    shares = [r["safe"].mean() for r in results if "safe" in r]
+    assert shares and min(shares) >= sq.SAFE_SHARE, (case["id"], min(shares))
+    undecided = [1.0 - r["decided"].mean() for r in results if "decided" in r]
+    assert bool(undecided) == s2.fgsm_ok(case["inner"])
+    assert max(undecided or [0.0]) <= ac.UNDECIDED_CAP, (case["id"], max(undecided))
+    print("sequence %s: %d steps, least share of safe rows %.3f (%d checks), largest undecided share %.4f (%d signed ops)"
+          % (case["id"], steps[-1], min(shares), len(shares), max(undecided or [0.0]), len(undecided)))
+
+
+def test_the_budgets_tell_every_fault_of_the_second_draw(oracle_mod, modelled2):
+    """two budgets or more at the first check behind the hazard, but for the pairs of sequence_cases2.TWIN_ONLY (reasons there): any
+    distance shows in the bitwise comparison with the twin that the device test makes, and must be there"""
+    least, twin_only = {}, {}
+    for i in range(s2.N_LONE):
+        case, results, snaps = modelled2[i]
+        for fault in s2.FAULTS:
+            f = s2.fault_factor(oracle_mod, case, fault, results, snaps)
+            applies = fault != "F12" or s2.fgsm_ok(case["inner"])          # (F12 needs a perturbing call)
+            assert (f is not None) == applies, "sequence %s and the hazard of %s" % (case["id"], fault)
+            if f is None:
+                continue
+            d = twin_only if (case["net"], fault) in s2.TWIN_ONLY else least
+            assert f >= (2.0 if d is least else 1e-3), "sequence %s: %s stays within %.3g budgets" % (case["id"], fault, f)
+            d[fault] = min(d.get(fault, np.inf), f)
+    assert set(least) == set(s2.FAULTS)
+    print("least distance of a faulty model, in budgets: " + "  ".join("%s %.3g" % (k, least[k]) for k in s2.FAULTS))
+    print("... and where the twin alone resolves it: " + "  ".join("%s %.3g" % (k, v) for k, v in twin_only.items()))
+    for k in s2.FAULTS:                                          # the table beside FAULT_FACTORS_FOUND is what this run finds
+        assert abs(least[k] / s2.FAULT_FACTORS_FOUND2[k] - 1.0) < 0.01, (k, least[k], s2.FAULT_FACTORS_FOUND2.get(k))
+
+
+@pytest.mark.parametrize("i", range(s2.N_GROUP))
+def test_every_group_sequence_of_the_second_draw_contains_every_pair(i):
+    case = s2.group_case(i)
+    ops, K = case["ops"], case["K"]
+    assert ops == s2.group_case(i)["ops"]
+    found = s2.group_pairs(ops)
+    assert sorted(found) == sorted(s2.PAIRS2), (case["id"], found)
+    assert {name for name, _ in ops} == set(s2.GROUP_OPS2)
+    assert {kw["op"][0] for name, kw in ops if name == "member"} == set(s2.MEMBER_READS)
+    assert {kw["k"] for name, kw in ops if name == "member"} <= {0, K // 2, K - 1}
+    loops = [kw for name, kw in ops if name == "g_train_held_out"]
+    assert any(isinstance(kw["B"], list) for kw in loops) and any(17 <= kw["iters"] <= 20 for kw in loops)
+    assert any(kw["held"] and kw["n"] > sq.MAX_BATCH for name, kw in ops if name == "g_evaluate_set")
+    for k in range(K):
+        lone = s2.member_case(case, k)["ops"]
+        assert all((op is None) == (o[0] == "g_ensemble_set" or (o[0] == "member" and o[1]["k"] != k)) for op, o in zip(lone, ops))
+    print("group sequence %s: %d ops, pairs at %s" % (case["id"], len(ops), " ".join("%s@%d" % (p, found[p][0]) for p in s2.PAIRS2)))
