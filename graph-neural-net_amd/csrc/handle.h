@@ -486,10 +486,17 @@ struct EvalScope { // for blocks above max_batch: the evaluation workspace's buf
 void free_eval_workspace(gnn_mlp *h);
 void free_input_grad(gnn_mlp *h); // (input_grad.hip; destroy_handle calls it)
 // input_grad.hip: behind a do_gradient on (a0, B), the launch over delta_1 . W_0^T -- the block's input gradient into h->gx
-// (the caller has made it), or with `fgsm` the rows a0 perturbed along its sign into fgsm->out (input_grad_kernel.h: fgsm_kernel;
-// out == a0 is allowed)
-struct FgsmStep { float eps, lo, hi; float *out; };
-void enqueue_input_grad(gnn_mlp *h, const float *a0, int B, const FgsmStep *fgsm = nullptr);
+// (the caller has made it), or with `step` the rows a0 moved along its sign into step->out (input_grad_kernel.h; out == a0 is
+// allowed).  The descriptor names the epilogue: origin == null, fgsm_kernel (a0 + eps * sign, clipped); otherwise pgd_kernel, one
+// projected step of size alpha around row `idx ? idx[b] : b` of `origin` (resident rows, leading dimension ld[0])
+struct AdvStep {
+    float eps, lo, hi; float *out;
+    float alpha = 0.f; const float *origin = nullptr; const int32_t *idx = nullptr;
+};
+void enqueue_input_grad(gnn_mlp *h, const float *a0, int B, const AdvStep *step = nullptr);
+// the start rows of the projected attack into h->act[0] (pgd_start_kernel): `origin` / `idx` as above, row0 the set index of the
+// block's first row (idx == null), n the iteration's number, seed < 0: the origin rows clipped to the box alone
+void enqueue_pgd_start(gnn_mlp *h, const AdvStep &step, int B, int64_t row0, int64_t seed, int n);
 void rccl_detach_handle(gnn_mlp *h); // (dp.hip; gnn_mlp_destroy calls it)
 bool can_defer_update(const gnn_mlp *h);
 int step_on_host_batch_deferred(gnn_mlp *h, int B, double step, double momentum); // act[0] / ybuf hold the staged batch

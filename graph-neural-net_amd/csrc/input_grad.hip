@@ -58,28 +58,42 @@ void widen(const float *src, double *dst, size_t n) {
 
 namespace gnn {
 namespace host {
-// gx = (delta_1 . W_0^T) * f'(a0) of the block do_gradient has just run on -- or, `fgsm`, the rows perturbed along the sign of
-// that gradient into fgsm->out (fgsm_kernel; gx is then neither needed nor written)
-void enqueue_input_grad(gnn_mlp *h, const float *a0, int B, const FgsmStep *fgsm) {
+// gx = (delta_1 . W_0^T) * f'(a0) of the block do_gradient has just run on -- or, `step`, the rows moved along the sign of that
+// gradient into step->out (fgsm_kernel, or with an origin pgd_kernel; gx is then neither needed nor written)
+void enqueue_input_grad(gnn_mlp *h, const float *a0, int B, const AdvStep *step) {
     const bool bf = h->dtype == GNN_DTYPE_BF16;
     InputGradParams p{};
     p.D = bf ? static_cast<const void *>(h->deltab[1]) : static_cast<const void *>(h->delta[1]);
     p.W = bf ? static_cast<const void *>(h->Wb + h->w_off[0]) : static_cast<const void *>(h->W + h->w_off[0]);
     p.A0 = a0; p.lda = h->ld[0];
-    p.GX = fgsm ? fgsm->out : h->gx; p.ldg = h->ld[0];
+    p.GX = step ? step->out : h->gx; p.ldg = h->ld[0];
     p.M = h->ld[0]; p.m_true = h->dims[0];
     p.K = h->ld[1];
     p.rows = B;
     p.act = h->inner_act;
     const dim3 grid((unsigned)((h->ld[0] / 16 + IG_WAVES - 1) / IG_WAVES), (unsigned)(pad_up(B) / 16));
-    if (fgsm) {
-        const FgsmParams q{p, fgsm->eps, fgsm->lo, fgsm->hi};
-        if (bf) hipLaunchKernelGGL(fgsm_kernel<true>, grid, dim3(IG_WAVES * 64), 0, h->stream, q);
+    if (step) {
+        const FgsmParams q{p, step->eps, step->lo, step->hi};
+        if (step->origin) {
+            const PgdParams s{q, step->alpha, step->origin, h->ld[0], step->idx};
+            if (bf) hipLaunchKernelGGL(pgd_kernel<true>, grid, dim3(IG_WAVES * 64), 0, h->stream, s);
+            else hipLaunchKernelGGL(pgd_kernel<false>, grid, dim3(IG_WAVES * 64), 0, h->stream, s);
+        } else if (bf) hipLaunchKernelGGL(fgsm_kernel<true>, grid, dim3(IG_WAVES * 64), 0, h->stream, q);
         else hipLaunchKernelGGL(fgsm_kernel<false>, grid, dim3(IG_WAVES * 64), 0, h->stream, q);
         return;
     }
     if (bf) hipLaunchKernelGGL(input_grad_kernel<true>, grid, dim3(IG_WAVES * 64), 0, h->stream, p);
     else hipLaunchKernelGGL(input_grad_kernel<false>, grid, dim3(IG_WAVES * 64), 0, h->stream, p);
+}
+void enqueue_pgd_start(gnn_mlp *h, const AdvStep &step, int B, int64_t row0, int64_t seed, int n) {
+    PgdStartParams p{};
+    p.X0 = step.origin; p.ldx0 = h->ld[0]; p.idx = step.idx;
+    p.out = h->act[0]; p.ldo = h->ld[0];
+    p.M = h->ld[0]; p.m_true = h->dims[0]; p.rows = B; p.rows_pad = pad_up(B);
+    p.row0 = (uint32_t)row0; p.seed = seed < 0 ? 0u : (uint32_t)seed; p.n = (uint32_t)n;
+    p.random = seed < 0 ? 0 : 1;
+    p.eps = step.eps; p.lo = step.lo; p.hi = step.hi;
+    hipLaunchKernelGGL(pgd_start_kernel, dim3(grid_for((int64_t)p.rows_pad * (p.M / 4))), dim3(256), 0, h->stream, p);
 }
 void free_input_grad(gnn_mlp *h) {
     if (h->gx) (void)hipFree(h->gx);

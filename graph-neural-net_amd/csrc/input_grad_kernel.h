@@ -15,6 +15,10 @@
 //                              accumulation is f32 either way, and one kernel body serves both; f' from the unrounded a0.
 //                              Rows >= `rows` and columns >= m_true are written as exact zeros (W_0's pad rows are 0).
 //   fgsm_kernel<BF>            the same product (ig_tile_product) with the perturbation a0 + eps * sign(g), clipped, as its epilogue
+//   pgd_kernel<BF>             ... with one step of the projected attack as its epilogue: a + alpha * sign(g), projected onto the
+//                              eps-ball around the row's ORIGIN (read from the resident rows, through the index vector for a
+//                              sampled batch), then clipped
+//   pgd_start_kernel           element-wise: the attack's start rows, the origin plus eps * u from a counter-based hash, clipped
 //   saliency_kernel            thread (column i, class c) walks the block's rows in row order and adds (double)|gx[b][i]| of the
 //                              rows whose expected class (confusion_kernel.h: expected_class, MT:186-188) is c into sal[c][i];
 //                              the running sum starts from the value the previous block left, so over a range it is ONE sum in row
@@ -136,6 +140,101 @@ static __global__ __launch_bounds__(IG_WAVES * 64) void fgsm_kernel(FgsmParams q
             o[r] = col + r < p.m_true ? fgsm_value(a[r], acc[r] * act_prime_from_a(p.act, a[r]), q.eps, q.lo, q.hi) : 0.f;
     }
     *reinterpret_cast<f32x4 *>(p.GX + (size_t)b * p.ldg + col) = o;
+}
+
+// One step of the projected attack (adversarial.hip: gnn_mlp_pgd_set_range ...) as the epilogue of the same product.  `a` is the
+// current iterate (f.g.A0), x0 the ORIGIN of the row -- row `idx ? idx[b] : b` of X0, the resident rows: the staging rows no
+// longer hold it after the first step -- and g the gradient at `a`, formed exactly as above.  In f32, every operation rounded on
+// its own:
+//   v  = a + alpha * s(g)
+//   w  = min(max(v, x0 - eps), x0 + eps)     the ball around the origin, each bound one rounding
+//   a' = min(max(w, lo), hi)                 the box last: alpha == eps on a == x0 is fgsm_value bit for bit (v is one of the bounds or x0)
+struct PgdParams {
+    FgsmParams f;    // f.g.A0: the iterate; f.g.GX / ldg: the next iterate
+    float alpha;
+    const float *X0; int ldx0; // the origin rows (leading dimension ldx0 >= f.g.M)
+    const int32_t *idx;        // the block's rows of X0, or null: rows 0 .. rows-1
+};
+__device__ inline float pgd_value(float a, float x0, float g, float alpha, float eps, float lo, float hi) {
+#pragma clang fp contract(off)
+    const float s = g > 0.f ? 1.f : g < 0.f ? -1.f : 0.f;
+    const float t = alpha * s;
+    const float v = a + t;
+    const float below = x0 - eps, above = x0 + eps;
+    const float w = fminf(fmaxf(v, below), above);
+    return fminf(fmaxf(w, lo), hi);
+}
+// grid as input_grad_kernel's.  In place (f.g.GX == f.g.A0, every step but the first of a range call without a random start) is
+// safe for fgsm_kernel's reason: a lane reads its own four cells of A0 and of the origin before it stores the same four cells, and
+// X0 is never the buffer written.  idx[b] is loaded for b < rows only; rows >= `rows` and columns >= m_true become exact zeros.
+template <bool BF>
+static __global__ __launch_bounds__(IG_WAVES * 64) void pgd_kernel(PgdParams q) {
+    const InputGradParams &p = q.f.g;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int fr = lane & 15, fq = lane >> 4;
+    const int i0 = (blockIdx.x * IG_WAVES + wave) * 16, b0 = blockIdx.y * 16;
+    if (i0 >= p.M) return; // (no barrier below)
+    const f32x4 acc = ig_tile_product<BF>(p, i0, b0, fr, fq);
+    const int b = b0 + fr, col = i0 + 4 * fq;
+    f32x4 o = {0.f, 0.f, 0.f, 0.f};
+    if (b < p.rows) {
+        const size_t origin = q.idx ? (size_t)q.idx[b] : (size_t)b;
+        const f32x4 a = *reinterpret_cast<const f32x4 *>(p.A0 + (size_t)b * p.lda + col);
+        const f32x4 x0 = *reinterpret_cast<const f32x4 *>(q.X0 + origin * q.ldx0 + col);
+#pragma unroll
+        for (int r = 0; r < 4; r++)
+            o[r] = col + r < p.m_true ? pgd_value(a[r], x0[r], acc[r] * act_prime_from_a(p.act, a[r]), q.alpha, q.f.eps, q.f.lo, q.f.hi) : 0.f;
+    }
+    *reinterpret_cast<f32x4 *>(p.GX + (size_t)b * p.ldg + col) = o;
+}
+
+// The start of the attack, element-wise, 16 B per lane over the pad(rows) x M staging rows: a_0 = min(max(x0 + eps * u, lo), hi)
+// with u in [-1, 1) from a counter-based hash of (seed, n, R, c) -- R the row's index in its resident set (row0 + b, or idx[b]),
+// c the column, n the iteration's number (0 for the range calls) -- in uint32 arithmetic that wraps:
+//   mix(u):  u ^= u >> 16; u *= 0x7feb352d; u ^= u >> 15; u *= 0x846ca68b; u ^= u >> 16
+//   r = mix(mix(mix(seed) + n) ^ R);  h = mix(r + 0x9E3779B9 * c);  u = float(h >> 8) * 2^-23 - 1      (exact)
+// `random` == 0: a_0 = x0 clipped to the box alone (steps == 0 without a seed).  Padding rows and columns: exact zeros.
+struct PgdStartParams {
+    const float *X0; int ldx0; const int32_t *idx; // the origin rows, as in PgdParams
+    float *out; int ldo;                           // pad(rows) x M
+    int M, m_true, rows, rows_pad;
+    uint32_t row0, seed, n;
+    int random;
+    float eps, lo, hi;
+};
+__device__ __host__ inline uint32_t pgd_mix(uint32_t u) {
+    u ^= u >> 16; u *= 0x7feb352du; u ^= u >> 15; u *= 0x846ca68bu; u ^= u >> 16;
+    return u;
+}
+__device__ inline float pgd_start_value(float x0, uint32_t row_key, uint32_t c, int random, float eps, float lo, float hi) {
+#pragma clang fp contract(off)
+    float v = x0;
+    if (random) {
+        const uint32_t h = pgd_mix(row_key + 0x9E3779B9u * c);
+        const float u = (float)(h >> 8) * 0x1p-23f - 1.f;
+        const float t = eps * u;
+        v = x0 + t;
+    }
+    return fminf(fmaxf(v, lo), hi);
+}
+static __global__ __launch_bounds__(256) void pgd_start_kernel(PgdStartParams p) {
+    const int m4 = p.M / 4;
+    const int64_t total = (int64_t)p.rows_pad * m4;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int b = (int)(i / m4);
+        const int col = 4 * (int)(i - (int64_t)b * m4);
+        f32x4 o = {0.f, 0.f, 0.f, 0.f};
+        if (b < p.rows) {
+            const uint32_t R = p.idx ? (uint32_t)p.idx[b] : p.row0 + (uint32_t)b;
+            const size_t origin = p.idx ? (size_t)p.idx[b] : (size_t)b;
+            const f32x4 x0 = *reinterpret_cast<const f32x4 *>(p.X0 + origin * p.ldx0 + col);
+            const uint32_t row_key = pgd_mix(pgd_mix(pgd_mix(p.seed) + p.n) ^ R);
+#pragma unroll
+            for (int r = 0; r < 4; r++)
+                o[r] = col + r < p.m_true ? pgd_start_value(x0[r], row_key, (uint32_t)(col + r), p.random, p.eps, p.lo, p.hi) : 0.f;
+        }
+        *reinterpret_cast<f32x4 *>(p.out + (size_t)b * p.ldo + col) = o;
+    }
 }
 
 constexpr int SAL_NT = 256;

@@ -463,6 +463,40 @@ class NeuralNet:
         _capi.check(self._lib.gnn_mlp_train_sampled_fgsm(self._h, sampler._h, int(iterations), int(batch), float(step),
                                                          float(momentum), float(eps), float(clip[0]), float(clip[1])))
 
+    # The iterated, projected attack (PGD; BIM with start_seed=None): per step a + alpha * sign(g), projected onto the eps-ball
+    # around the resident row, then clipped; start_seed selects a reproducible random start inside the ball (include/gnn_mlp.h).
+    @staticmethod
+    def _seed(start_seed):
+        return -1 if start_seed is None else int(start_seed)
+
+    def pgd_range(self, eps, alpha, steps, first=0, n=None, clip=(0.0, 1.0), held_out=False, start_seed=None):
+        """The attacked rows [first, first + n) after `steps` steps, (n, d_0); steps=1, alpha=eps, no start seed is fgsm_range bit
+        for bit; steps=0 returns the start rows.  One readback."""
+        first, n = self._rows(first, n, held_out)
+        out = np.empty((max(n, 0), self.layer_dims[0]), dtype=np.float64)
+        _capi.check(self._lib.gnn_mlp_pgd_set_range(self._h, int(bool(held_out)), first, n, float(eps), float(alpha), int(steps),
+                                                    self._seed(start_seed), float(clip[0]), float(clip[1]), _dp(out)))
+        return out
+
+    def evaluate_pgd_range(self, eps, alpha, steps, first=0, n=None, clip=(0.0, 1.0), held_out=False, start_seed=None, curve=False):
+        """Robust (hits, loss_sum) after `steps` steps; curve=True: two arrays of steps + 1 entries, entry t the state after t steps
+        (entry 0: the start rows), each what the call with steps=t returns."""
+        first, n = self._rows(first, n, held_out)
+        steps = int(steps)
+        slots = steps + 1 if curve else 1
+        hits, loss = np.zeros(max(slots, 1), dtype=np.int64), np.zeros(max(slots, 1), dtype=np.float64)
+        _capi.check(self._lib.gnn_mlp_evaluate_pgd_set_range(
+            self._h, int(bool(held_out)), first, n, float(eps), float(alpha), steps, self._seed(start_seed), float(clip[0]),
+            float(clip[1]), int(bool(curve)), hits.ctypes.data_as(C.POINTER(C.c_int64)), _dp(loss)))
+        return (hits, loss) if curve else (int(hits[0]), float(loss[0]))
+
+    def train_sampled_pgd(self, sampler, iterations, batch, step, momentum, eps, alpha, steps, clip=(0.0, 1.0), start_seed=None):
+        """Adversarial training with the iterated attack: train_sampled's loop, every iteration stepping on its own batch after
+        `steps` projected steps against the weights of that moment."""
+        _capi.check(self._lib.gnn_mlp_train_sampled_pgd(self._h, sampler._h, int(iterations), int(batch), float(step),
+                                                        float(momentum), float(eps), float(alpha), int(steps),
+                                                        self._seed(start_seed), float(clip[0]), float(clip[1])))
+
     # -- data-parallel hooks ------------------------------------------------------------------
     @property
     def grad_elems(self):

@@ -253,6 +253,57 @@ def fgsm(net, X, Y, eps, clip=(0.0, 1.0)):
     return out if clip is None else np.clip(out, clip[0], clip[1])
 
 
+def _pgd_mix(u):
+    u = u ^ (u >> np.uint32(16))
+    u = u * np.uint32(0x7feb352d)
+    u = u ^ (u >> np.uint32(15))
+    u = u * np.uint32(0x846ca68b)
+    return u ^ (u >> np.uint32(16))
+
+
+def pgd_start(X, eps, clip=(0.0, 1.0), start_seed=0, first_row=0, iteration=0):
+    """The random start of the projected attack (include/gnn_mlp.h) in numpy: float32 rows a_0 = clip(x0 + eps * u), u in [-1, 1)
+    from the hash of (start_seed, iteration, row index in the resident set, column), uint32 arithmetic that wraps.  first_row: the
+    set index of the first row, or one index per row (a sampled batch)."""
+    x0 = np.atleast_2d(np.asarray(X, dtype=np.float32))
+    rows = np.asarray(first_row, dtype=np.int64)
+    rows = (rows + np.arange(x0.shape[0])) if rows.ndim == 0 else rows.reshape(-1)
+    if rows.shape[0] != x0.shape[0]:
+        raise ValueError("one row index per row")
+    with np.errstate(over="ignore"):
+        seed = _pgd_mix(np.array([int(start_seed)], dtype=np.uint32)) + np.uint32(int(iteration) & 0xFFFFFFFF)
+        r = _pgd_mix(_pgd_mix(seed) ^ (rows & 0xFFFFFFFF).astype(np.uint32))
+        h = _pgd_mix(r[:, None] + np.uint32(0x9E3779B9) * np.arange(x0.shape[1], dtype=np.uint32)[None, :])
+    u = (h >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -23) - np.float32(1.0)
+    v = x0 + np.float32(eps) * u
+    return np.minimum(np.maximum(v, np.float32(clip[0])), np.float32(clip[1]))
+
+
+def pgd(net, X, Y, eps, alpha, steps, clip=(0.0, 1.0), start_seed=None, first_row=0, iteration=0):
+    """The projected attack on host rows: `steps` times a + alpha * sign(g), g = net.input_gradient(a, Y), projected onto the
+    eps-ball around X and then clipped, from X or (start_seed) from pgd_start's rows; steps=0 returns the start rows clipped.  The
+    host route: one synchronising gradient call per step, the formula and the start carried in numpy float32 exactly as the device
+    calls define them (NeuralNet.pgd_range, evaluate_pgd_range, train_sampled_pgd), for any inner activation.  first_row and
+    iteration key the start as those calls do: the set index of the first row (or one index per row) and the iteration's number."""
+    single = np.ndim(X) == 1
+    x0 = np.atleast_2d(np.asarray(X, dtype=np.float32))
+    Y = np.atleast_2d(np.asarray(Y, dtype=np.float64))
+    eps_f, alpha_f, lo, hi = np.float32(eps), np.float32(alpha), np.float32(clip[0]), np.float32(clip[1])
+    below, above = x0 - eps_f, x0 + eps_f
+    box = lambda a: np.minimum(np.maximum(a, lo), hi)
+    if start_seed is not None:
+        a = pgd_start(x0, eps, clip, start_seed, first_row, iteration)
+    else:
+        a = x0 if steps > 0 else box(x0)
+    for _ in range(int(steps)):
+        g = np.atleast_2d(net.input_gradient(a.astype(np.float64), Y))
+        s = (g > 0).astype(np.float32) - (g < 0).astype(np.float32)
+        v = a + alpha_f * s
+        a = box(np.minimum(np.maximum(v, below), above))
+    out = a.astype(np.float64)
+    return out[0] if single else out
+
+
 def train_log_row(net_dim, iterations, step_size, batch_size, momentum, noise, training_acc, test_acc):
     """The row MNISTTrainer.logTest appends to logs/trainLog.csv (MT:211-219):
     `dims,iterations,step,batch,momentum,noise,trainAcc,testAcc` in the reference's number formats

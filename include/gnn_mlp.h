@@ -562,6 +562,50 @@ int gnn_mlp_evaluate_fgsm_set_range(gnn_mlp_t *h, int set, int64_t first, int64_
 int gnn_mlp_train_sampled_fgsm(gnn_mlp_t *h, gnn_sampler_t *s, int iterations, int batch, double step, double momentum, double eps,
                                double lo, double hi);
 
+/* ---- adversarial rows (projected gradient descent; BIM without the random start) ------------------
+ * The iterated, projected form of the perturbation above (csrc/adversarial.hip; the kernels: csrc/input_grad_kernel.h, pgd_kernel
+ * and pgd_start_kernel).  The current iterate is a, the ORIGIN x0 is the resident row, g the input gradient of the current weights
+ * at a, formed exactly as gnn_mlp_input_gradient forms it.  All arithmetic is f32, every operation rounded on its own (no fused
+ * multiply-add); eps_f, alpha_f, lo_f, hi_f are the f32 values of the call's doubles.  One step:
+ *   s  = (g > 0) - (g < 0)                        s(0) = 0, a NaN g leaves s = 0
+ *   v  = a + alpha_f * s
+ *   w  = min(max(v, x0 - eps_f), x0 + eps_f)      the ball around the ORIGIN, each bound one rounding
+ *   a' = min(max(w, lo_f), hi_f)                  the box last
+ * The box comes last: a row outside [lo, hi] ends inside it, as with the one-step call, and steps == 1, alpha == eps, no random
+ * start is bit for bit gnn_mlp_fgsm_set_range's result.  After `steps` steps the result is a_T; steps == 0 is allowed and returns
+ * the start rows clipped to the box.
+ * Random start: start_seed < 0 starts at x0 (the first step then moves x0 itself, unclipped).  0 <= start_seed < 2^31 starts at
+ *   mix(u):  u ^= u >> 16;  u *= 0x7feb352d;  u ^= u >> 15;  u *= 0x846ca68b;  u ^= u >> 16          (uint32, wrapping)
+ *   r = mix(mix(mix(seed) + n) ^ R),   h = mix(r + 0x9E3779B9 * c),   u = float(h >> 8) * 2^-23 - 1   (exact, in [-1, 1))
+ *   a_0 = min(max(x0 + eps_f * u, lo_f), hi_f)                                                         (two roundings, then the box)
+ * with R the row's index IN ITS RESIDENT SET (first + ... for the range calls, the drawn dataset index in training), c the
+ * column, n = 0 for the range calls and the iteration's number within the call in training.  The start cannot leave the ball
+ * (rounding is monotonic).
+ * Domain and refusals are the one-step calls', through the same check (lone nets, the three inner activations, 0 <= lo <= hi, eps
+ * finite and not negative, non-negative rows as the caller's precondition); in addition alpha negative or not finite, steps < 0
+ * or > 1024, start_seed >= 2^31 -> GNN_ERR_BAD_ARG.
+ * Per block of at most max_batch rows: the start (pgd_start_kernel into the staging rows; none when start_seed < 0 and
+ * steps >= 1, the first step then reads the resident rows directly), then per step the handle's gradient computation without an
+ * update on the current rows and pgd_kernel in place, the origin read from the resident rows.  No host work and no
+ * synchronisation between steps or blocks.  What the range calls overwrite and leave is what the one-step range calls do; the
+ * look-ahead state is left as the last gradient computation leaves it -- gnn_mlp_compute_gradient_range on the last block when
+ * steps == 1 on the training set without a start, a gradient computation on a host batch otherwise. */
+/* the attacked rows themselves (fp64 of the f32 values) */
+int gnn_mlp_pgd_set_range(gnn_mlp_t *h, int set, int64_t first, int64_t n, double eps, double alpha, int steps, int64_t start_seed,
+                          double lo, double hi, double *X_adv /* [n][d_0] */);
+/* Robust hits and loss with the reductions of gnn_mlp_evaluate_fgsm_set_range.  curve == 0: one entry, the state after step
+ * `steps`.  curve == 1: steps + 1 entries, entry t the state after t steps, entry 0 the start rows (one more forward pass and two
+ * reductions per step and block; one fill, one readback).  Entry t is bit for bit what the call with steps = t, curve = 0
+ * returns.  Either output may be null, not both; curve other than 0 / 1 -> GNN_ERR_BAD_ARG. */
+int gnn_mlp_evaluate_pgd_set_range(gnn_mlp_t *h, int set, int64_t first, int64_t n, double eps, double alpha, int steps,
+                                   int64_t start_seed, double lo, double hi, int curve, int64_t *hits, double *loss_sum);
+/* Adversarial training with the iterated attack: gnn_mlp_train_sampled_fgsm's loop, every iteration a gather of the drawn rows,
+ * the start, `steps` x (gradient computation without an update, pgd_kernel with the origin read from the resident training rows
+ * through the iteration's index vector), then the step on the attacked rows.  Draws, chunks, refusals and the sampler's end state
+ * are gnn_mlp_train_sampled's; the step count advances once per iteration. */
+int gnn_mlp_train_sampled_pgd(gnn_mlp_t *h, gnn_sampler_t *s, int iterations, int batch, double step, double momentum, double eps,
+                              double alpha, int steps, int64_t start_seed, double lo, double hi);
+
 /* ---- shape specialisation ---------------------------------------------------------------------
  * The per-row-block kernel of the fused small-net path is a template over the net's shape; with
  * compile-time layer sizes it is ~1.5x faster than with sizes read from kernel arguments.
