@@ -14,5 +14,5 @@ from .neural_net import (  # noqa: F401
     LOSS_HALF_SQUARED, OUT_ACT_LOSS, OUT_SOFTMAX_CE, REDUCE_DIRECT, REDUCE_DIRECT_RS, REDUCE_RCCL, DataParallelNeuralNet, GeneralNeuralNet,
     NetGroup, NeuralNet, SoftmaxCrossEntropyNeuralNet, best_point, smooth_labels)
 from .trainer import (  # noqa: F401
-    NetGroupTrainer, NeuralNetTrainer, Sampler, accuracy, fgsm, log_test, per_class, pgd, pgd_start, read_idx_images, read_idx_labels,
-    train_log_row)
+    NetGroupTrainer, NeuralNetTrainer, Sampler, accuracy, convergence_delta, fgsm, integrated_gradients, log_test, per_class, pgd,
+    pgd_start, read_idx_images, read_idx_labels, train_log_row)

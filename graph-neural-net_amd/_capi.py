@@ -131,6 +131,8 @@ SYMBOLS = [
                                                  C.c_double, C.c_double, C.c_int, C.POINTER(C.c_int64), _dp]),
     ("gnn_mlp_train_sampled_pgd", C.c_int, [_H, _H, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int,
                                             C.c_int64, C.c_double, C.c_double]),
+    ("gnn_mlp_integrated_gradients_set_range", C.c_int, [_H, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_double, _dp, _dp,
+                                                         C.POINTER(C.c_int64), _dp]),
     ("gnn_mlp_forget_lookahead", C.c_int, [_H]),
     ("gnn_mlp_advance_time", C.c_int, [_H, C.c_int]),
     ("gnn_mlp_recover_stream", C.c_int, [_H]),

@@ -15,13 +15,22 @@
 using namespace gnn;
 using namespace gnn::host;
 
-namespace {
-
-int check_fgsm_args(const gnn_mlp *h, double eps, double lo, double hi, AdvStep *out) {
+namespace gnn {
+namespace host {
+int check_adv_net(const gnn_mlp *h) {
     if (h->group || h->dp_replica) return fail(GNN_ERR_STATE, "the adversarial calls serve lone nets, not members of a group or replicas");
     if (h->inner_act != GNN_ACT_LEAKY_RELU && h->inner_act != GNN_ACT_RELU && h->inner_act != GNN_ACT_IDENTITY)
         return fail(GNN_ERR_UNSUPPORTED, "the device holds f(x), not x: the perturbation needs an inner activation that is the identity on "
                                          "non-negative inputs (leaky ReLU, ReLU, identity)");
+    return GNN_OK;
+}
+} // namespace host
+} // namespace gnn
+
+namespace {
+
+int check_fgsm_args(const gnn_mlp *h, double eps, double lo, double hi, AdvStep *out) {
+    TRY(check_adv_net(h));
     if (!(eps >= 0) || !std::isfinite(eps)) return fail(GNN_ERR_BAD_ARG, "eps must be finite and not negative");
     if (!(lo >= 0) || !(hi >= lo)) return fail(GNN_ERR_BAD_ARG, "clip bounds must satisfy 0 <= lo <= hi: the device holds f(x), which is x on non-negative values only");
     *out = AdvStep{(float)eps, (float)lo, (float)hi, h->act[0]};

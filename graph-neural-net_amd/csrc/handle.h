@@ -176,6 +176,8 @@ struct gnn_mlp {
     // the input gradient of the block last run through input_grad.hip: pad(max_batch) x ld[0], made on first use, never a slice
     // of a group's arena
     float *gx = nullptr;
+    // the running sum of integrated gradients (intgrad_kernel): the same shape, made on first use, freed where gx is
+    float *gsum = nullptr;
 
     // one process per GPU with the exchange inside the library's step loop (gnn_mlp_rccl_*, dp.hip): this rank's communicator
     void *rccl_comm = nullptr; int rccl_ranks = 0, rccl_rank = 0;
@@ -497,6 +499,9 @@ void enqueue_input_grad(gnn_mlp *h, const float *a0, int B, const AdvStep *step 
 // the start rows of the projected attack into h->act[0] (pgd_start_kernel): `origin` / `idx` as above, row0 the set index of the
 // block's first row (idx == null), n the iteration's number, seed < 0: the origin rows clipped to the box alone
 void enqueue_pgd_start(gnn_mlp *h, const AdvStep &step, int B, int64_t row0, int64_t seed, int n);
+// adversarial.hip: the nets whose staging rows may be moved on the device -- lone nets (GNN_ERR_STATE for a member of a group or a
+// replica) whose inner activation is the identity on non-negative values (GNN_ERR_UNSUPPORTED otherwise: the device holds f(x))
+int check_adv_net(const gnn_mlp *h);
 void rccl_detach_handle(gnn_mlp *h); // (dp.hip; gnn_mlp_destroy calls it)
 bool can_defer_update(const gnn_mlp *h);
 int step_on_host_batch_deferred(gnn_mlp *h, int B, double step, double momentum); // act[0] / ybuf hold the staged batch

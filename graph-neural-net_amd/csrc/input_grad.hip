@@ -5,10 +5,14 @@
 // groups input_grad_combine_kernel).  No host work between blocks; the results come back in ONE readback at the end of a call.
 // Like gnn_mlp_compute_gradient*, a call leaves the gradient buffer holding its last block's weight gradient; it changes no
 // weight, momentum, step count or sampler.
+// gnn_mlp_integrated_gradients_set_range: per block the first path point into the staging rows, then per point the gradient
+// computation on the staging rows and intgrad_kernel (the running sum, the next point in place, last the attribution into gx),
+// then the same consumers and, for the completeness check, two forward passes and intgrad_delta_kernel.
 #include "handle.h"
 #include "input_grad_kernel.h"
 
 #include <algorithm>
+#include <cmath>
 
 using namespace gnn;
 using namespace gnn::host;
@@ -54,6 +58,50 @@ void widen(const float *src, double *dst, size_t n) {
     for (size_t i = 0; i < n; i++) dst[i] = (double)src[i];
 }
 
+// ---- integrated gradients: intgrad_kernel, intgrad_start_kernel, intgrad_delta_kernel ------------------------------------------
+constexpr int INTGRAD_MAX_STEPS = 1024;
+
+int ensure_gsum(gnn_mlp *h) {
+    if (h->gsum) return GNN_OK;
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&h->gsum), sizeof(float) * (size_t)h->cap_rows * h->ld[0]));
+    return GNN_OK;
+}
+
+// act[0] = baseline + alpha * (x0 - baseline) of the block's rows, and on a bf16 handle its shadow (the forward passes read it)
+void enqueue_intgrad_point(gnn_mlp *h, const float *x0, int B, float alpha, float baseline) {
+    IntGradStartParams p{};
+    p.X0 = x0; p.ldx0 = h->ld[0];
+    p.out = h->act[0]; p.ldo = h->ld[0];
+    p.M = h->ld[0]; p.m_true = h->dims[0]; p.rows = B; p.rows_pad = pad_up(B);
+    p.alpha = alpha; p.bl = baseline;
+    hipLaunchKernelGGL(intgrad_start_kernel, dim3(grid_for((int64_t)p.rows_pad * (p.M / 4))), dim3(256), 0, h->stream, p);
+    if (h->dtype == GNN_DTYPE_BF16) to_bf16(h, h->act[0], h->actb[0], (size_t)pad_up(B) * h->ld[0]);
+}
+
+// behind a do_gradient on the staging rows: path point k of m -- the sum, then the next point in place or the attribution in gx
+void enqueue_intgrad_step(gnn_mlp *h, const float *x0, int B, int k, int m, float alpha_next, float baseline) {
+    const bool bf = h->dtype == GNN_DTYPE_BF16;
+    IntGradParams q{};
+    InputGradParams &p = q.g;
+    p.D = bf ? static_cast<const void *>(h->deltab[1]) : static_cast<const void *>(h->delta[1]);
+    p.W = bf ? static_cast<const void *>(h->Wb + h->w_off[0]) : static_cast<const void *>(h->W + h->w_off[0]);
+    p.A0 = h->act[0]; p.lda = h->ld[0];
+    p.GX = h->gx; p.ldg = h->ld[0];
+    p.M = h->ld[0]; p.m_true = h->dims[0];
+    p.K = h->ld[1];
+    p.rows = B;
+    p.act = h->inner_act;
+    q.A = h->act[0];
+    q.X0 = x0; q.ldx0 = h->ld[0];
+    q.S = h->gsum; q.lds = h->ld[0];
+    q.k = k; q.m = m;
+    q.alpha_next = alpha_next; q.bl = baseline; q.mf = (float)m;
+    const dim3 grid((unsigned)((h->ld[0] / 16 + IG_WAVES - 1) / IG_WAVES), (unsigned)(pad_up(B) / 16));
+    if (bf) hipLaunchKernelGGL(intgrad_kernel<true>, grid, dim3(IG_WAVES * 64), 0, h->stream, q);
+    else hipLaunchKernelGGL(intgrad_kernel<false>, grid, dim3(IG_WAVES * 64), 0, h->stream, q);
+    if (bf && k < m - 1) to_bf16(h, h->act[0], h->actb[0], (size_t)pad_up(B) * h->ld[0]);
+}
+
 } // namespace
 
 namespace gnn {
@@ -97,7 +145,8 @@ void enqueue_pgd_start(gnn_mlp *h, const AdvStep &step, int B, int64_t row0, int
 }
 void free_input_grad(gnn_mlp *h) {
     if (h->gx) (void)hipFree(h->gx);
-    h->gx = nullptr;
+    if (h->gsum) (void)hipFree(h->gsum);
+    h->gx = h->gsum = nullptr;
 }
 } // namespace host
 } // namespace gnn
@@ -158,6 +207,74 @@ return guarded([&]() -> int {
         for (int i = 0; i < d_out; i++) class_rows[i] = (int64_t)c[i];
     }
     if (grad) widen(reinterpret_cast<const float *>(reinterpret_cast<const char *>(host.data()) + head), grad, (size_t)n * d0);
+    return GNN_OK;
+}); }
+
+int gnn_mlp_integrated_gradients_set_range(gnn_mlp_t *h, int set, int64_t first, int64_t n, int steps, double baseline,
+                                           double *attributions, double *maps, int64_t *class_rows, double *delta) {
+return guarded([&]() -> int {
+    TRY(check_handle(h));
+    if (!attributions && !maps && !class_rows && !delta) return fail(GNN_ERR_BAD_ARG, "every output is null");
+    TRY(check_adv_net(h));
+    if (!(baseline >= 0) || !std::isfinite(baseline))
+        return fail(GNN_ERR_BAD_ARG, "baseline must be finite and not negative: the device holds f(x), which is x on non-negative values only");
+    if (steps < 1 || steps > INTGRAD_MAX_STEPS) return fail(GNN_ERR_BAD_ARG, "steps must lie in 1 .. 1024");
+    TRY(check_set_rows(h, set, first, n));
+    TRY(ensure_gx(h));
+    TRY(ensure_gsum(h));
+    const ResidentSet rs = resident_set(h, set);
+    const int Lm = h->L - 1, d0 = h->dims[0], d_out = h->dims[Lm], m = steps;
+    const float bl = (float)baseline;
+    std::vector<float> alpha((size_t)m + 1, 0.f); // alpha_k = (float)((k + 0.5) / m); alpha_m is never used
+    for (int k = 0; k < m; k++) alpha[k] = (float)(((double)k + 0.5) / (double)m);
+    // [d_out x d0 sums][d_out row counts] (one fill) | n deltas | the rows' attributions without padding: one readback;
+    // behind them, not read back, the rows' losses L_x
+    const size_t cells = (size_t)d_out * d0;
+    static_assert(sizeof(unsigned long long) == sizeof(double), "one buffer for sums and counters");
+    const size_t head = sizeof(double) * (cells + (size_t)d_out), delta_b = delta ? sizeof(double) * (size_t)n : 0;
+    const size_t attr_b = attributions ? sizeof(float) * (size_t)n * d0 : 0, lx_b = delta ? sizeof(float) * (size_t)n : 0;
+    DevScratch res;
+    TRY(res.alloc(head + delta_b + attr_b + lx_b));
+    HIP_TRY(hipMemsetAsync(res.p, 0, head, h->stream));
+    double *d_sal = res.as<double>();
+    unsigned long long *d_rows = reinterpret_cast<unsigned long long *>(d_sal + cells);
+    double *d_delta = reinterpret_cast<double *>(res.as<char>() + head);
+    float *d_attr = reinterpret_cast<float *>(res.as<char>() + head + delta_b);
+    float *d_lx = reinterpret_cast<float *>(res.as<char>() + head + delta_b + attr_b);
+    const int block = h->max_batch;
+    for (int64_t off = 0; off < n; off += block) {
+        const int B = (int)std::min<int64_t>(block, n - off);
+        const float *x0 = rs.X + (size_t)(first + off) * h->ld[0];
+        const float *y = rs.Y + (size_t)(first + off) * h->ld[Lm];
+        enqueue_intgrad_point(h, x0, B, alpha[0], bl);
+        for (int k = 0; k < m; k++) {
+            do_gradient(h, h->act[0], y, B, false, 0.f, 0.f, false);
+            enqueue_intgrad_step(h, x0, B, k, m, alpha[(size_t)k + 1], bl);
+        }
+        if (maps || class_rows) enqueue_saliency(h, h->stream, h->gx, y, B, maps ? d_sal : nullptr, class_rows ? d_rows : nullptr);
+        if (attributions) TRY(enqueue_row_copy(h, h->stream, h->gx, B, d_attr + (size_t)off * d0));
+        if (delta) { // the completeness check: the losses of the rows and of the baseline rows (gx is no forward pass's buffer)
+            do_forward(h, x0, y, B, false, true, false);
+            HIP_TRY(hipMemcpyAsync(d_lx + off, h->lossv, sizeof(float) * (size_t)B, hipMemcpyDeviceToDevice, h->stream));
+            enqueue_intgrad_point(h, x0, B, 0.f, bl);
+            do_forward(h, h->act[0], y, B, false, true, false);
+            const IntGradDeltaParams dp{h->gx, h->ld[0], d0, B, d_lx + off, h->lossv, d_delta + off};
+            hipLaunchKernelGGL(intgrad_delta_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, h->stream, dp);
+        }
+    }
+    TRY_LAUNCHES(h);
+    const size_t back = head + delta_b + attr_b;
+    std::vector<double> host((back + 7) / 8);
+    HIP_TRY(hipMemcpyAsync(host.data(), res.p, back, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (maps) std::memcpy(maps, host.data(), sizeof(double) * cells);
+    if (class_rows) {
+        const unsigned long long *c = reinterpret_cast<const unsigned long long *>(host.data() + cells);
+        for (int i = 0; i < d_out; i++) class_rows[i] = (int64_t)c[i];
+    }
+    const char *tail = reinterpret_cast<const char *>(host.data()) + head;
+    if (delta) std::memcpy(delta, tail, delta_b);
+    if (attributions) widen(reinterpret_cast<const float *>(tail + delta_b), attributions, (size_t)n * d0);
     return GNN_OK;
 }); }
 

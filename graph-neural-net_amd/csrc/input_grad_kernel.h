@@ -1,6 +1,7 @@
 // input_grad_kernel.h -- which inputs the loss depends on: g = d calculateLoss(x, y) / d x (NN:27, SCE:207-220, GNN:230-242),
 // the l = 0 continuation of the backward loop the reference stops at delta_1 (SCE:272-278), and what consumes it on the device
-// (input_grad.hip: gnn_mlp_input_gradient*, gnn_mlp_group_input_gradient_range; adversarial.hip: gnn_mlp_fgsm_set_range ...).
+// (input_grad.hip: gnn_mlp_input_gradient*, gnn_mlp_group_input_gradient_range, gnn_mlp_integrated_gradients_set_range;
+// adversarial.hip: gnn_mlp_fgsm_set_range ...).
 //   input_grad_kernel<BF>      gx[b][i] = f'(a0[b][i]) * sum_j delta_1[b][j] * W_0[i][j]: pad(B) rows, ld[0] columns, contraction
 //                              over ld[1].  f' from a0 = f(x) (the reference applies f to the raw input too, SCE:183-186): for the
 //                              leaky pair `a <= 0 ? 0.01 : 1` (MT:235), so an exact-zero pixel gets 0.01.  Both operands are
@@ -19,6 +20,10 @@
 //                              eps-ball around the row's ORIGIN (read from the resident rows, through the index vector for a
 //                              sampled batch), then clipped
 //   pgd_start_kernel           element-wise: the attack's start rows, the origin plus eps * u from a counter-based hash, clipped
+//   intgrad_kernel<BF>         ... with one path point of integrated gradients as its epilogue: the running sum of g, the next
+//                              point into the staging rows, on the last point the attribution (x0 - baseline) * mean g
+//   intgrad_start_kernel       element-wise: a path point baseline + alpha * (x0 - baseline) (the first one; alpha 0: the baseline)
+//   intgrad_delta_kernel       thread per row: sum of the row's attributions in fp64 minus (loss(x) - loss(baseline))
 //   saliency_kernel            thread (column i, class c) walks the block's rows in row order and adds (double)|gx[b][i]| of the
 //                              rows whose expected class (confusion_kernel.h: expected_class, MT:186-188) is c into sal[c][i];
 //                              the running sum starts from the value the previous block left, so over a range it is ONE sum in row
@@ -235,6 +240,112 @@ static __global__ __launch_bounds__(256) void pgd_start_kernel(PgdStartParams p)
         }
         *reinterpret_cast<f32x4 *>(p.out + (size_t)b * p.ldo + col) = o;
     }
+}
+
+// Integrated gradients (input_grad.hip: gnn_mlp_integrated_gradients_set_range): one of m path points per launch, the step's
+// bookkeeping as the epilogue of the same product.  x0 is the ORIGIN row (the resident rows), bl the baseline, `a` the staging
+// point the gradient was taken at (g.A0), g formed exactly as above.  In f32, every operation rounded on its own:
+//   d = x0 - bl;   S_0 = g(a_0),  S_k = S_{k-1} + g(a_k);   a_{k+1} = bl + alpha_{k+1} * d;   IG = d * (S_{m-1} / m_f)
+// Step k < m - 1 stores S_k into S and a_{k+1} into the staging rows (`A`, the buffer g.A0 names); the last step stores IG into
+// g.GX.  S is not read at k == 0: what an earlier block or call left there cannot leak.
+struct IntGradParams {
+    InputGradParams g;         // g.A0: the path point a_k; g.GX / ldg: the attribution (written by the last step only)
+    float *A;                  // the staging rows again, to write a_{k+1} (leading dimension g.lda)
+    const float *X0; int ldx0; // the origin rows (never written)
+    float *S; int lds;         // the running sum, pad(rows) x M
+    int k, m;
+    float alpha_next, bl, mf;  // alpha_{k+1}, the baseline, (float)m
+};
+__device__ inline float intgrad_sum(float acc, float fprime, float s_prev, bool first) {
+#pragma clang fp contract(off) // (the product is input_grad_kernel's g, rounded before it is added)
+    const float g = acc * fprime;
+    return first ? g : s_prev + g;
+}
+__device__ inline float intgrad_point(float x0, float bl, float alpha) {
+#pragma clang fp contract(off)
+    const float d = x0 - bl;
+    const float t = alpha * d;
+    return bl + t;
+}
+__device__ inline float intgrad_value(float x0, float bl, float s, float mf) {
+#pragma clang fp contract(off)
+    const float d = x0 - bl;
+    const float mean = s / mf;
+    return d * mean;
+}
+// grid as input_grad_kernel's.  In place is safe for fgsm_kernel's reason: a lane reads its own four cells of A0, of the origin
+// and of S before it stores the same four cells of S and of the staging rows.  Rows >= `rows` and columns >= m_true of every
+// buffer a step writes become exact zeros.
+template <bool BF>
+static __global__ __launch_bounds__(IG_WAVES * 64) void intgrad_kernel(IntGradParams q) {
+    const InputGradParams &p = q.g;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int fr = lane & 15, fq = lane >> 4;
+    const int i0 = (blockIdx.x * IG_WAVES + wave) * 16, b0 = blockIdx.y * 16;
+    if (i0 >= p.M) return; // (no barrier below)
+    const f32x4 acc = ig_tile_product<BF>(p, i0, b0, fr, fq);
+    const int b = b0 + fr, col = i0 + 4 * fq;
+    const bool first = q.k == 0, last = q.k == q.m - 1;
+    f32x4 s = {0.f, 0.f, 0.f, 0.f}, o = {0.f, 0.f, 0.f, 0.f};
+    if (b < p.rows) {
+        const f32x4 a = *reinterpret_cast<const f32x4 *>(p.A0 + (size_t)b * p.lda + col);
+        const f32x4 x0 = *reinterpret_cast<const f32x4 *>(q.X0 + (size_t)b * q.ldx0 + col);
+        f32x4 sp = {0.f, 0.f, 0.f, 0.f};
+        if (!first) sp = *reinterpret_cast<const f32x4 *>(q.S + (size_t)b * q.lds + col);
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            if (col + r >= p.m_true) continue;
+            s[r] = intgrad_sum(acc[r], act_prime_from_a(p.act, a[r]), sp[r], first);
+            o[r] = last ? intgrad_value(x0[r], q.bl, s[r], q.mf) : intgrad_point(x0[r], q.bl, q.alpha_next);
+        }
+    }
+    if (last) {
+        *reinterpret_cast<f32x4 *>(p.GX + (size_t)b * p.ldg + col) = o;
+    } else {
+        *reinterpret_cast<f32x4 *>(q.S + (size_t)b * q.lds + col) = s;
+        *reinterpret_cast<f32x4 *>(q.A + (size_t)b * p.lda + col) = o;
+    }
+}
+
+// A path point, element-wise, 16 B per lane over the pad(rows) x M staging rows: a = bl + alpha * (x0 - bl) (intgrad_point), the
+// first point a_0 -- or, alpha == 0, the baseline rows themselves (bl + 0 * d is bl for every finite d).  Padding: exact zeros.
+struct IntGradStartParams {
+    const float *X0; int ldx0;
+    float *out; int ldo;
+    int M, m_true, rows, rows_pad;
+    float alpha, bl;
+};
+static __global__ __launch_bounds__(256) void intgrad_start_kernel(IntGradStartParams p) {
+    const int m4 = p.M / 4;
+    const int64_t total = (int64_t)p.rows_pad * m4;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int b = (int)(i / m4);
+        const int col = 4 * (int)(i - (int64_t)b * m4);
+        f32x4 o = {0.f, 0.f, 0.f, 0.f};
+        if (b < p.rows) {
+            const f32x4 x0 = *reinterpret_cast<const f32x4 *>(p.X0 + (size_t)b * p.ldx0 + col);
+#pragma unroll
+            for (int r = 0; r < 4; r++) o[r] = col + r < p.m_true ? intgrad_point(x0[r], p.bl, p.alpha) : 0.f;
+        }
+        *reinterpret_cast<f32x4 *>(p.out + (size_t)b * p.ldo + col) = o;
+    }
+}
+
+// The completeness check: delta[r] = sum_i IG[r][i] - (L_x[r] - L_b[r]), one thread per live row, the row's cells summed in fp64
+// in column order (no atomics: the same bits on every run).  L_x / L_b: the per-row losses of the rows and of the baseline rows.
+struct IntGradDeltaParams {
+    const float *IG; int ldg;
+    int d0, rows;
+    const float *Lx, *Lb;
+    double *delta;
+};
+static __global__ __launch_bounds__(64) void intgrad_delta_kernel(IntGradDeltaParams p) {
+    const int r = blockIdx.x * 64 + threadIdx.x;
+    if (r >= p.rows) return;
+    const float *row = p.IG + (size_t)r * p.ldg;
+    double sum = 0.0;
+    for (int i = 0; i < p.d0; i++) sum += (double)row[i];
+    p.delta[r] = sum - ((double)p.Lx[r] - (double)p.Lb[r]);
 }
 
 constexpr int SAL_NT = 256;

@@ -497,6 +497,26 @@ class NeuralNet:
                                                         float(momentum), float(eps), float(alpha), int(steps),
                                                         self._seed(start_seed), float(clip[0]), float(clip[1])))
 
+    # -- integrated gradients on the device: csrc/input_grad.hip ----------------------------------------
+    def integrated_gradients_range(self, steps, baseline=0.0, first=0, n=None, held_out=False, maps=False, delta=False):
+        """The attributions (n, d_0) of calculateLoss to the inputs of rows [first, first + n): (x - baseline) times the mean input
+        gradient over `steps` midpoints of the straight path from the baseline (one scalar >= 0) to the row, in f32 as
+        include/gnn_mlp.h defines it.  maps=True appends (maps (d_out, d_0), class_rows (d_out,)): the sums of |attribution| over
+        the rows of each expected class and their numbers; delta=True appends the completeness gap (n,): the row's attributions
+        summed minus (calculateLoss(row) - calculateLoss(baseline)).  The domain is fgsm_range's; one readback."""
+        first, n = self._rows(first, n, held_out)
+        d0, d = self.layer_dims[0], self.layer_dims[-1]
+        ig = np.empty((max(n, 0), d0))
+        sal = np.zeros((d, d0)) if maps else None
+        rows = np.zeros(d, dtype=np.int64) if maps else None
+        gap = np.empty(max(n, 0)) if delta else None
+        _capi.check(self._lib.gnn_mlp_integrated_gradients_set_range(
+            self._h, int(bool(held_out)), first, n, int(steps), float(baseline), _dp(ig), _dp(sal) if maps else None,
+            rows.ctypes.data_as(C.POINTER(C.c_int64)) if maps else None, _dp(gap) if delta else None))
+        if not maps and not delta:
+            return ig
+        return (ig,) + ((sal, rows) if maps else ()) + ((gap,) if delta else ())
+
     # -- data-parallel hooks ------------------------------------------------------------------
     @property
     def grad_elems(self):

@@ -304,6 +304,42 @@ def pgd(net, X, Y, eps, alpha, steps, clip=(0.0, 1.0), start_seed=None, first_ro
     return out[0] if single else out
 
 
+def integrated_gradients(net, X, Y, steps, baseline=0.0):
+    """Integrated gradients of calculateLoss on host rows: (X - baseline) times the mean of net.input_gradient over `steps` midpoints
+    a_k = baseline + alpha_k * (X - baseline), alpha_k = float32((k + 0.5) / steps), of the straight path from the baseline (one
+    scalar) to the row.  The host route: one synchronising gradient call per point, the formula carried in numpy float32 exactly
+    as the device call defines it (NeuralNet.integrated_gradients_range), for any inner activation."""
+    single = np.ndim(X) == 1
+    x0 = np.atleast_2d(np.asarray(X, dtype=np.float32))
+    Y = np.atleast_2d(np.asarray(Y, dtype=np.float64))
+    m = int(steps)
+    if m < 1:
+        raise ValueError("steps must be at least 1")
+    b, mf = np.float32(baseline), np.float32(m)
+    d = x0 - b
+    s = None
+    for k in range(m):
+        a = b + np.float32((k + 0.5) / m) * d
+        g = np.atleast_2d(net.input_gradient(a.astype(np.float64), Y)).astype(np.float32)
+        s = g if s is None else s + g
+    out = (d * (s / mf)).astype(np.float64)
+    return out[0] if single else out
+
+
+def convergence_delta(net, X, Y, ig, baseline=0.0):
+    """The completeness gap of attributions `ig` of rows X, one value per row: sum_i ig[r][i] - (calculateLoss(x_r) -
+    calculateLoss(baseline row)), in fp64 from net.calculateLoss in blocks of net.max_batch rows.  Zero up to the path rule's
+    error for integrated gradients; what NeuralNet.integrated_gradients_range(delta=True) computes on the device."""
+    X = np.atleast_2d(np.asarray(X, dtype=np.float64))
+    Y = np.atleast_2d(np.asarray(Y, dtype=np.float64))
+    ig = np.atleast_2d(np.asarray(ig, dtype=np.float64))
+    base = np.full(X.shape, float(np.float32(baseline)))
+    mb = int(getattr(net, "max_batch", len(X)))
+    lx = np.concatenate([np.atleast_1d(net.calculateLoss(X[o:o + mb], Y[o:o + mb])) for o in range(0, len(X), mb)])
+    lb = np.concatenate([np.atleast_1d(net.calculateLoss(base[o:o + mb], Y[o:o + mb])) for o in range(0, len(X), mb)])
+    return ig.sum(axis=1) - (lx - lb)
+
+
 def train_log_row(net_dim, iterations, step_size, batch_size, momentum, noise, training_acc, test_acc):
     """The row MNISTTrainer.logTest appends to logs/trainLog.csv (MT:211-219):
     `dims,iterations,step,batch,momentum,noise,trainAcc,testAcc` in the reference's number formats

@@ -606,6 +606,37 @@ int gnn_mlp_evaluate_pgd_set_range(gnn_mlp_t *h, int set, int64_t first, int64_t
 int gnn_mlp_train_sampled_pgd(gnn_mlp_t *h, gnn_sampler_t *s, int iterations, int batch, double step, double momentum, double eps,
                               double alpha, int steps, int64_t start_seed, double lo, double hi);
 
+/* ---- integrated gradients -----------------------------------------------------------------------
+ * The attribution of calculateLoss to the inputs along the straight path from a baseline to the row (csrc/input_grad.hip; the
+ * kernels: csrc/input_grad_kernel.h, intgrad_kernel, intgrad_start_kernel, intgrad_delta_kernel).  x0 is the resident row, b_f and
+ * m_f the f32 values of `baseline` and `steps` = m, g(a) the input gradient of the current weights at a, formed exactly as
+ * gnn_mlp_input_gradient forms it.  All arithmetic is f32, every operation rounded on its own.  The path points are midpoints,
+ * alpha_k = (float)((k + 0.5) / m), formed in double and rounded once, k = 0 .. m-1:
+ *   d    = x0 - b_f                              one rounding
+ *   a_k  = b_f + alpha_k * d                     product, then sum
+ *   S_0  = g(a_0);   S_k = S_{k-1} + g(a_k)      step order
+ *   IG   = d * (S_{m-1} / m_f)                   division, then product
+ * Domain: the adversarial calls', through the same check -- lone nets (GNN_ERR_STATE for a member of a group or a replica),
+ * leaky ReLU, ReLU or identity inside (GNN_ERR_UNSUPPORTED otherwise: the device holds f(x)), non-negative rows as the caller's
+ * precondition.  baseline is one scalar, finite and >= 0 (0: the black image), 1 <= steps <= 1024; GNN_ERR_BAD_ARG otherwise.
+ * Every a_k is then >= 0 (fl(x0 - b_f) >= -b_f and rounding is monotonic), a valid f(x).  A baseline ROW, groups, ensembles,
+ * sampled and training forms are not served.
+ * Per block of at most max_batch rows: the first point into the staging rows, then m x (the handle's gradient computation
+ * without an update on the staging rows, intgrad_kernel in place); the block's attributions end in the input-gradient buffer.
+ * No host work and no synchronisation between steps or blocks; one fill, one readback.
+ * Outputs, any of them null, not all: the attributions (fp64 of the f32 values); maps[c][i], the sum of |IG[.][i]| over the rows
+ * whose expected class (MT:186-188) is c, in fp64 in row order, and class_rows[c], their number (the reductions of
+ * gnn_mlp_input_gradient_range); delta[r] = sum_i IG[r][i] - (calculateLoss(x0_r) - calculateLoss(baseline row)), the
+ * completeness check: the row's cells summed in fp64 in column order, the two f32 per-row losses from one forward pass over the
+ * block's rows and one over baseline rows (two more forward passes per block).
+ * The call applies a pending host-batch update first and changes no weight, momentum, step count, sampler or look-ahead state
+ * (its gradient computations are those of a host batch).  It overwrites the staging rows, activations, deltas and the
+ * input-gradient buffer, and like gnn_mlp_compute_gradient* leaves the gradient buffer with its last block's weight gradient
+ * (at the last path point). */
+int gnn_mlp_integrated_gradients_set_range(gnn_mlp_t *h, int set, int64_t first, int64_t n, int steps, double baseline,
+                                           double *attributions /* [n][d_0] */, double *maps /* [d_out][d_0] */,
+                                           int64_t *class_rows /* [d_out] */, double *delta /* [n] */);
+
 /* ---- shape specialisation ---------------------------------------------------------------------
  * The per-row-block kernel of the fused small-net path is a template over the net's shape; with
  * compile-time layer sizes it is ~1.5x faster than with sizes read from kernel arguments.
